@@ -1,6 +1,6 @@
 """RealNVP 64x64x3 NLL training throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One step = the train.py:176-200 body on synthetic data: logit_transform of a
@@ -11,9 +11,16 @@ s/t network in bf16 with fp32 accumulation (couplings, log-det, BN stats,
 master weights and Adam in fp32).  Data parallel over RCCL for N > 1 (weak
 scaling: 64 images per GPU).
 
-Prints ONE JSON line (rank 0) with images/sec (whole job), bits/dim, the
-per-kernel roofline of the dominant kernel family and the CPU oracle timed
-on this host.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line
+(rank 0) with images/sec (whole job), ms_per_step and bits/dim.
+--dump-outputs DIR also writes what the last timed step computed to
+DIR/<name>.npy (dump_outputs); that step then starts from the run's initial
+state, so that its outputs are the same in every run (timed_with_rewind).
+--full adds everything that takes runs of its own to the same line: the
+per-kernel roofline of the dominant kernel family (one instrumented eager
+step), the data-parallel diagnostics, the secondary measurements (fp32
+parity mode, drop-in loop, sampling, configs 3 and 4) and the CPU oracle
+timed on this host.
 """
 import argparse
 import json
@@ -58,9 +65,16 @@ def parse():
     p.add_argument("--overlap", action="store_true", help="side stream for weight gradients (HIP graphs serialise it today)")
     p.add_argument("--comm", default="overlap", choices=["overlap", "split"], help="DP all-reduce schedule")
     p.add_argument("--reduce-dtype", default="fp32", choices=["fp32", "bf16"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one computed to DIR/<name>.npy (dump_outputs)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the instrumented eager step (per-kernel "
+                        "roofline, kernel families), the data-parallel diagnostics, the secondary measurements and "
+                        "the CPU baseline")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the secondary measurements (fp32 parity mode, drop-in loop, sampling, config 3)")
+                   help="with --full: skip the secondary measurements (fp32 parity mode, drop-in loop, sampling, "
+                        "configs 3 and 4)")
     p.add_argument("--cpu-batch", type=int, default=64)
     p.add_argument("--cpu-steps", type=int, default=3)
     p.add_argument("--seed", type=int, default=0)
@@ -79,6 +93,10 @@ def parse():
                    help="capture a marker dispatch around every engine launch INTO the step graph and write the "
                         "families here (for a rocprofv3 kernel trace split by family, tools/trace_families.py)")
     a = p.parse_args()
+    if a.pmc_markers and not a.full:
+        p.error("--pmc-markers marks the instrumented eager step, which only --full runs")
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[a.config]
     for k in ("batch", "size", "res_blocks", "base_dim"):
         if getattr(a, k) is None:
@@ -269,6 +287,81 @@ def timed(fn, steps, warmup, barrier=lambda: None):
     torch.cuda.synchronize()
     barrier()
     return time.perf_counter() - t0
+
+
+def timed_with_rewind(tr, snap, steps, barrier):
+    """The timed region of a --dump-outputs run: steps - 1 timed steps, then
+    -- outside the clock -- the trainer is put back to `snap` (parameters, Adam
+    moments, step counter and with it the noise stream, BatchNorm buffers; the
+    packed weight images are re-derived from the parameters), then the last
+    timed step.  Returns the sum of the two timed segments.
+
+    Why: the kernels' floating-point atomics sum in an order that varies from
+    run to run (relative 1e-7 after one step), and the first Adam steps on a
+    random initialisation amplify that to O(1) in the gradients within five
+    steps, so the state after W + K - 1 steps is not reproducible.  Started
+    from `snap`, the last timed step computes the same from the same inputs
+    in every run, up to that rounding, and it is what dump_outputs writes.
+    A step's launches and their sizes do not depend on the values, so its
+    time is that of any other step; the log-likelihood sum of the earlier
+    timed steps is kept."""
+    dt = timed(tr.step, steps - 1, 0, barrier)
+    ll = tr.ll_acc.clone()
+    tr._restore(snap)
+    tr.ll_acc.copy_(ll)
+    tr._ensure_packed()
+    return dt + timed(tr.step, 1, 0, barrier), float(ll.item())
+
+
+DUMP_ARENA_SAMPLE = 1 << 21     # elements kept of each flat arena (8 MB in float32)
+
+
+def dump_outputs(tr, last_ll, out_dir):
+    """What the timed path left after its last step, as out_dir/<name>.npy:
+
+      log_prob                 per-image log p of the last step's logit-
+                               transformed batch: prior + the flow's
+                               log-det, without the transform's own (float32)
+      x_logit                  that batch after the logit transform (float32)
+      mean_log_likelihood      last_ll: the last step's batch mean of
+                               log_prob + the logit transform's log-det
+                               (float64, what bits_per_dim averages)
+      param, grad, exp_avg, exp_avg_sq
+                               the flat parameter / gradient / Adam arenas
+                               after the last update (float32)
+      bn_buffers               every floating-point module buffer (BatchNorm
+                               running statistics), concatenated (float32)
+
+    An arena longer than DUMP_ARENA_SAMPLE is written at a fixed sample of its
+    indices (PCG64 seed 0, sorted; the same for every run of one model), the
+    indices themselves in arena_index.npy: 4 arenas x 8 MB stay far below
+    64 MB in all.  Model weights, pixels and the dequantisation noise are
+    functions of --seed and the step counter alone, so two runs with the same
+    arguments compute on the same inputs, and the last timed step starts
+    from the run's initial state (timed_with_rewind), so two runs of one
+    build write the same arrays up to the rounding of one step's atomics
+    (measured, config 1, relative L2: grad 7e-8, exp_avg 7e-8, param 2e-9;
+    x_logit, log_prob and bn_buffers bitwise equal)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def save(name, t, dtype=np.float32):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy().astype(dtype, copy=False))
+    save("log_prob", tr.lp)
+    save("x_logit", tr.xl)
+    np.save(os.path.join(out_dir, "mean_log_likelihood.npy"), np.array([last_ll], dtype=np.float64))
+    idx = None
+    if tr.n > DUMP_ARENA_SAMPLE:
+        rng = np.random.Generator(np.random.PCG64(0))
+        idx_np = np.sort(rng.integers(0, tr.n, size=DUMP_ARENA_SAMPLE, dtype=np.int64))
+        np.save(os.path.join(out_dir, "arena_index.npy"), idx_np.astype(np.float64))
+        idx = torch.from_numpy(idx_np).to(tr.param.device)
+    for name in ("param", "grad", "exp_avg", "exp_avg_sq"):
+        t = getattr(tr, name)
+        save(name, t if idx is None else t.index_select(0, idx))
+    bufs = [b.detach().reshape(-1).float() for _, b in tr.model.named_buffers() if b.is_floating_point()]
+    if bufs:
+        save("bn_buffers", torch.cat(bufs))
 
 
 def secondary(args, dev):
@@ -509,10 +602,17 @@ def main():
             import torch.distributed as dist
             dist.barrier()
 
+    # --dump-outputs: the state the first step starts from, kept so that the
+    # last timed step can start from it again (timed_with_rewind)
+    snap = tr._snapshot() if args.dump_outputs else None
     for _ in range(args.warmup):
         tr.step()
     tr.reset_metrics()
-    dt = timed(tr.step, args.steps, 0, barrier)
+    if snap is None:
+        dt = timed(tr.step, args.steps, 0, barrier)
+    else:
+        dt, ll_before_last = timed_with_rewind(tr, snap, args.steps, barrier)
+        del snap
     mean_ll = tr.mean_logll(args.steps)
     if pg is not None:
         dt = max_over_ranks(dt, dev, pg)
@@ -520,9 +620,13 @@ def main():
     bpd = tr.bits_per_dim(mean_ll)
     imgs = world * args.batch * args.steps
     value = imgs / dt
-    dp = dp_diagnostics(tr, pg, dt / args.steps, dev) if pg is not None else None
-    roof, fams = kernel_roofline(tr, args.pmc_markers if rank == 0 else None, args.traffic, cfg_key, args.mfma,
-                                 args.rocprof_families)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, tr.mean_logll(1) - ll_before_last, args.dump_outputs)
+    dp, roof, fams = None, None, None
+    if args.full:
+        dp = dp_diagnostics(tr, pg, dt / args.steps, dev) if pg is not None else None
+        roof, fams = kernel_roofline(tr, args.pmc_markers if rank == 0 else None, args.traffic, cfg_key, args.mfma,
+                                     args.rocprof_families)
     alg_bytes = CONFIGS[args.config]["alg_bytes"]
     label = CONFIGS[args.config]["label"]
     if args.custom:
@@ -560,11 +664,11 @@ def main():
             out["dp"] = dp
     del tr, model
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         out["secondary"] = secondary(args, dev)
-    # the CPU baseline on rank 0 at every world size, after the timed region
-    # (the other ranks wait at the closing barrier; --cpu-steps bounds it)
-    if rank == 0 and not args.no_cpu_baseline:
+    # --full: the CPU baseline on rank 0 at every world size, after the timed
+    # region (the other ranks wait at the closing barrier; --cpu-steps bounds it)
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -24,7 +24,7 @@ if [ -z "$NOTEST" ]; then
   step pytest_gpu.log timeout -k 10 1000 python -u -m pytest tests -m gpu -v -rf --timeout 300 --timeout-method thread
   step smoke.log timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
-B="python3 $R/bench.py --no-cpu-baseline --no-secondary --no-graph --steps 1 --warmup 1 --pmc-markers $R/$O/markers.json"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-secondary --no-graph --steps 1 --warmup 1 --pmc-markers $R/$O/markers.json"
 step pmc_fetch.log timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d $R/$O/pmc_fetch -o run -- $B
 step pmc_write.log timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d $R/$O/pmc_write -o run -- $B
 step pmc_mfma.log timeout -s KILL 150 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $R/$O/pmc_mfma -o run -- $B
@@ -34,4 +34,4 @@ step trace_fam.log timeout -k 10 300 rocprofv3 --kernel-trace --output-format cs
 step rocprof_families.txt python3 tools/trace_families.py $(find $O/trace_fam -name "*kernel_trace.csv" | head -1) $O/graph_markers.json $O/rocprof_families.json
 step prof.log timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o run -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary
 step step.txt python3 tools/step_dump.py $(find $O/prof -name "*kernel_trace.csv" | head -1)
-step bench.log timeout -k 10 600 python -u bench.py --traffic $O/pmc_traffic.json --mfma $O/pmc_mfma.json --rocprof-families $O/rocprof_families.json
+step bench.log timeout -k 10 600 python -u bench.py --full --traffic $O/pmc_traffic.json --mfma $O/pmc_mfma.json --rocprof-families $O/rocprof_families.json

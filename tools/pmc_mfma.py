@@ -1,6 +1,6 @@
 """Per-family MFMA utilisation of the training step from one rocprofv3 --pmc
 pass (SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE) over
-``bench.py --pmc-markers <markers.json>`` (eager instrumented step, markers
+``bench.py --full --pmc-markers <markers.json>`` (eager instrumented step, markers
 around every engine launch).
 
     python tools/pmc_mfma.py <pmc_dir> <markers.json> [out.json]

@@ -5,8 +5,8 @@
 The passes are produced by (one counter set per run, see MI355X_MICROARCH.md
 HBM section):
 
-    rocprofv3 --pmc FETCH_SIZE -d <fetch_dir> -o run -- python3 bench.py --pmc-markers <markers.json> ...
-    rocprofv3 --pmc WRITE_SIZE -d <write_dir> -o run -- python3 bench.py --pmc-markers <markers.json> ...
+    rocprofv3 --pmc FETCH_SIZE -d <fetch_dir> -o run -- python3 bench.py --full --pmc-markers <markers.json> ...
+    rocprofv3 --pmc WRITE_SIZE -d <write_dir> -o run -- python3 bench.py --full --pmc-markers <markers.json> ...
 
 bench.py's instrumented step dispatches an empty ``k_marker`` before and
 after every engine launch and writes the launch families in order to
