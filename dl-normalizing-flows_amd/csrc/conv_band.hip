@@ -7,7 +7,7 @@
 // One workgroup per CU walks a contiguous run of pixel bands (BM = 64*TM
 // pixels, whole image rows at 64x64 / 32x32):
 //   * the packed weights, the BatchNorm tables and the bias go to LDS ONCE per
-//     workgroup (the one-band-per-workgroup kernel, conv.hip k_conv_band,
+//     workgroup (the one-band-per-workgroup kernel, conv_band1.hip k_conv_band,
 //     reloaded its 19-75 KB of weights for every band, in dependent rounds);
 //   * bands are double buffered: band k+1's rows + halo are loaded into
 //     registers before band k's MFMAs and written (BN+ReLU'd) into the other

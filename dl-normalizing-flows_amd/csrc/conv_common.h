@@ -1,7 +1,10 @@
-// Device helpers shared by the conv kernel translation units (conv.hip,
-// conv_deep.hip): MFMA step per operand type, LDS swizzle, BN-statistics
-// shards, the fused 4-channel epilogue, register BN tables, fast division.
-// Included inside each file's anonymous namespace.
+// Device helpers shared by the conv kernel translation units (one kernel
+// family per file: conv_tiled.hip, conv_stream.hip, conv_halo.hip,
+// conv_band1.hip, conv_band.hip, conv_s1.hip, conv_deep.hip, wgrad.hip,
+// wgrad_tap.hip, ...): MFMA step per operand type, LDS swizzle, BN-statistics
+// shards, the fused 4-channel epilogue, register BN tables, fast division --
+// each file's own copy, in an anonymous namespace.  Below them, the launchers
+// the families export to rnvp_conv2d's dispatch (conv.hip).
 #pragma once
 #include <math.h>
 
@@ -409,7 +412,28 @@ __device__ __forceinline__ void bn_bwd_body(const rnvp_bn_bwd_args& a, double* d
     else bn_bwd_run<T, false>(a, dsm, blk, nblk);
 }
 
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
 }  // namespace
+
+// LDS-tiled implicit-GEMM conv with split-K (conv_tiled.hip): every conv that
+// passes rnvp_conv2d's checks
+int rnvp_conv_tiled_launch(const rnvp_conv_args* a, hipStream_t s);
+
+// register-streaming conv (conv_stream.hip): RNVP_E_UNSUPPORTED outside
+// n <= 64 / cs_in <= 64 / packed weights within 48 KiB of LDS
+int rnvp_conv_stream_launch(const rnvp_conv_args* a, hipStream_t s);
+
+// halo-tile conv (conv_halo.hip): RNVP_E_UNSUPPORTED outside M <= 1024 (3x3:
+// 4096) / 64 <= cs_in <= 1024 / n > 16 / BN sources of <= 2 stat shards
+int rnvp_conv_halo_launch(const rnvp_conv_args* a, hipStream_t s);
+
+// one-band-per-workgroup 3x3 conv (conv_band1.hip), the fallback where
+// rnvp_conv_band2_launch declines: RNVP_E_UNSUPPORTED outside
+// rnvp_conv_band_ok, the domain of both band kernels (3x3 / n, cs_in <= 64 /
+// 32k <= M < 2^21 / band + weights within 150 KiB of LDS)
+bool rnvp_conv_band_ok(const rnvp_conv_args* a);
+int rnvp_conv_band1_launch(const rnvp_conv_args* a, hipStream_t s);
 
 // deep-scale conv family (conv_deep.hip): number of configurations and the
 // launcher of configuration cfg (RNVP_E_UNSUPPORTED when it does not apply)
@@ -438,6 +462,12 @@ struct rnvp_group_kargs {
     int n;
 };
 rnvp_group_kargs group_kargs(const rnvp_net_step* steps, int n);
+
+// the deep family's kernels per (dtype, configuration): defined in
+// conv_deep_launch.h, instantiated by conv_deep_inst.hip once per pair
+using GroupKernel = void (*)(const rnvp_group_kargs);
+template <typename T, int CFG> int rnvp_deep_cfg_launch(const rnvp_conv_args* a, hipStream_t s, bool dry);
+template <typename T, int CFG> GroupKernel rnvp_deep_cfg_group(int nc, bool fm);
 int rnvp_s1_fanout_prepare(rnvp_net_step* steps, int n, int* klass, int* grid, int* lds_bytes);
 int rnvp_s1_fanout_launch(const rnvp_group_kargs& g, int klass, int grid, int lds_bytes, hipStream_t s);
 

@@ -1,5 +1,5 @@
-// Deep-scale conv family, device side (included by conv_deep.hip): the
-// per-tile body and its LDS size.
+// Deep-scale conv family, device side (included by conv_deep.hip and
+// conv_deep_launch.h): the per-tile body and its LDS size.
 #pragma once
 #include <stdlib.h>
 

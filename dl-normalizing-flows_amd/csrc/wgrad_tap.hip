@@ -4,7 +4,7 @@
 //
 //   dW[co][t*cs_in + ci] = sum_p dy[p][co] * act(x)[p + off(t)][ci]     (+ bias: sum_p dy[p][co])
 //
-// The round-2 kernel (conv.hip k_wgrad_grouped) gave every tap of a 3x3 its own
+// The round-2 kernel (wgrad.hip k_wgrad_grouped) gave every tap of a 3x3 its own
 // 64x64 (co x k) tile: the activation rows were re-read, re-decoded and
 // re-transformed (BN+ReLU) once per tap and per co tile, and each 64-pixel
 // stage cost ~350 VALU instructions against 8 MFMAs (PMC: 4.7 % MFMA busy).
