@@ -91,16 +91,49 @@ __device__ __forceinline__ void stg(bf16_t* p, float v) { *(RNVP_GLOBAL bf16_t*)
 // addition, so no FMA contraction is left to the compiler: the kernels that
 // inline this (k_adam, k_adam_gather, k_wn_adam) compute bitwise the same
 // update from the same operands.
+// c = the step control's grad_scale (clip_grad_norm_'s factor on the whole
+// p.grad: g and the regulariser's gradient, not Adam's weight decay).  c g and
+// 2 reg c are single roundings that are exact for c = 1.0f, so the unclipped
+// update keeps its bits.  The rounding error of c g (fmaf(c, g, -cg), exact;
+// 0 for c = 1.0f) is added back after the weight-decay FMA: where wd p and
+// c g nearly cancel (0.3 % of a real gradient arena) it is all that is left
+// of the product's low bits, and gr stays within two roundings of ITSELF
+// instead of one rounding of c g.  SCALED = false (no step control) is the
+// unscaled update itself: the kernels instantiate both, so a launch without
+// a control block runs the code it always ran.
+template <bool SCALED = false>
 __device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, int f, float b1, float b2, float eps,
-                                           float wd, float reg, float step_size, float inv_bc2s) {
-    float gr = fmaf(wd, p, g);
-    if (f == 2) gr = fmaf(2.f * reg, p, gr);
+                                           float wd, float reg, float step_size, float inv_bc2s, float c = 1.0f) {
+    float gr;
+    if (SCALED) {
+        const float cg = c * g;
+        gr = fmaf(wd, p, cg) + fmaf(c, g, -cg);
+        if (f == 2) gr = fmaf(2.f * reg * c, p, gr);
+    } else {
+        gr = fmaf(wd, p, g);
+        if (f == 2) gr = fmaf(2.f * reg, p, gr);
+    }
     m = fmaf(1.f - b1, gr - m, m);
     const float t = (1.f - b2) * gr;
     v = fmaf(v, b2, t * gr);
     const float den = fmaf(sqrtf(v), inv_bc2s, eps);
     return p - (step_size * m) / den;
 }
+
+// The per-launch scalars of the Adam kernels, by one thread into LDS:
+// coef = {lr / (1 - b1^t), 1 / sqrt(1 - b2^t), gradient scale}, t = *step +
+// step_add; the learning rate and the scale come from the step control when
+// there is one (rnvp_adam_args.ctl).
+__device__ __forceinline__ void adam_coef(const long long* step, long long step_add, float lr, float b1, float b2,
+                                          const rnvp_step_ctl* ctl, float* coef) {
+    const double t = (double)(step[0] + step_add);
+    const double bc1 = 1.0 - pow((double)b1, t), bc2 = 1.0 - pow((double)b2, t);
+    coef[0] = (float)((ctl ? ctl->lr : lr) / bc1);
+    coef[1] = (float)(1.0 / sqrt(bc2));
+    coef[2] = ctl ? ctl->grad_scale : 1.0f;
+}
+// a skipped step (non-finite gradient norm): the Adam kernels touch nothing
+__device__ __forceinline__ bool adam_skipped(const rnvp_step_ctl* ctl) { return ctl && ctl->skip; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -4,7 +4,7 @@
 
 #include "coupling_common.h"
 
-extern "C" int rnvp_version(void) { return 107; }
+extern "C" int rnvp_version(void) { return 108; }
 
 extern "C" int rnvp_struct_size(int which) {
     switch (which) {
@@ -20,6 +20,7 @@ extern "C" int rnvp_struct_size(int which) {
         case 9: return (int)sizeof(rnvp_net_step);
         case 10: return (int)sizeof(rnvp_range);
         case 11: return (int)sizeof(rnvp_link_args);
+        case 12: return (int)sizeof(rnvp_step_ctl);
     }
     return -1;
 }
@@ -532,18 +533,16 @@ extern "C" int rnvp_sumsq_bwd_multi(const rnvp_tensor_ref* refs, int n_refs, con
 // ---------------------------------------------------------------------------
 __global__ void k_step_inc(long long* step) { step[0] += 1; }
 
+template <bool CTL>
 __global__ void k_adam(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
                        float4* __restrict__ v, long long n4, const long long* step, long long step_add, float lr,
-                       float b1, float b2, float eps, float wd, const uint32_t* __restrict__ regm, float reg) {
-    __shared__ float sh[2];
-    if (threadIdx.x == 0) {
-        double t = (double)(step[0] + step_add);
-        double bc1 = 1.0 - pow((double)b1, t), bc2 = 1.0 - pow((double)b2, t);
-        sh[0] = (float)(lr / bc1);
-        sh[1] = (float)(1.0 / sqrt(bc2));
-    }
+                       float b1, float b2, float eps, float wd, const uint32_t* __restrict__ regm, float reg,
+                       const rnvp_step_ctl* ctl) {
+    __shared__ float sh[3];
+    if (CTL && adam_skipped(ctl)) return;
+    if (threadIdx.x == 0) adam_coef(step, step_add, lr, b1, b2, CTL ? ctl : nullptr, sh);
     __syncthreads();
-    const float step_size = sh[0], inv_bc2s = sh[1];
+    const float step_size = sh[0], inv_bc2s = sh[1], gclip = CTL ? sh[2] : 1.0f;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
         const uint32_t mk = regm ? regm[i] : 0x01010101u;
@@ -552,7 +551,7 @@ __global__ void k_adam(float4* __restrict__ p, const float4* __restrict__ g, flo
         for (int j = 0; j < 4; ++j) {
             const uint32_t f = (mk >> (8 * j)) & 0xff;
             if (f == 0) continue;                      // frozen parameter
-            pa[j] = adam_elem(pa[j], ga[j], ma[j], va[j], (int)f, b1, b2, eps, wd, reg, step_size, inv_bc2s);
+            pa[j] = adam_elem<CTL>(pa[j], ga[j], ma[j], va[j], (int)f, b1, b2, eps, wd, reg, step_size, inv_bc2s, gclip);
         }
         p[i] = pp; m[i] = mm; v[i] = vv;
     }
@@ -569,9 +568,9 @@ extern "C" int rnvp_adam_step(float* param, float* grad, float* exp_avg, float* 
     RNVP_LAUNCH_CHECK();
     if (n == 0) return RNVP_OK;
     long long n4 = n / 4;
-    k_adam<<<rnvp_grid(n4, 256, 8192), 256, 0, s>>>((float4*)param, (const float4*)grad, (float4*)exp_avg,
+    k_adam<false><<<rnvp_grid(n4, 256, 8192), 256, 0, s>>>((float4*)param, (const float4*)grad, (float4*)exp_avg,
                                                    (float4*)exp_avg_sq, n4, step, 0, lr, beta1, beta2, eps, weight_decay,
-                                                   (const uint32_t*)reg_mask, reg_coef);
+                                                   (const uint32_t*)reg_mask, reg_coef, nullptr);
     RNVP_LAUNCH_CHECK();
     return RNVP_OK;
 }
@@ -584,9 +583,26 @@ extern "C" int rnvp_adam_update(float* param, float* grad, float* exp_avg, float
     if (reg_mask && (((uintptr_t)reg_mask) & 3)) return RNVP_E_INVALID;
     if (n == 0) return RNVP_OK;
     const long long n4 = n / 4;
-    k_adam<<<rnvp_grid(n4, 256, 8192), 256, 0, (hipStream_t)stream>>>(
+    k_adam<false><<<rnvp_grid(n4, 256, 8192), 256, 0, (hipStream_t)stream>>>(
         (float4*)param, (const float4*)grad, (float4*)exp_avg, (float4*)exp_avg_sq, n4, step, step_add, lr, beta1,
-        beta2, eps, weight_decay, (const uint32_t*)reg_mask, reg_coef);
+        beta2, eps, weight_decay, (const uint32_t*)reg_mask, reg_coef, nullptr);
+    RNVP_LAUNCH_CHECK();
+    return RNVP_OK;
+}
+
+extern "C" int rnvp_adam_range(const rnvp_adam_args* ad, long long n, void* stream) {
+    if (!ad || n < 0 || (n & 3)) return RNVP_E_INVALID;
+    if (!ad->param || !ad->grad || !ad->exp_avg || !ad->exp_avg_sq || !ad->step) return RNVP_E_INVALID;
+    if ((((uintptr_t)ad->param) | ((uintptr_t)ad->grad) | ((uintptr_t)ad->exp_avg) | ((uintptr_t)ad->exp_avg_sq)) & 15)
+        return RNVP_E_INVALID;
+    if (ad->mask && (((uintptr_t)ad->mask) & 3)) return RNVP_E_INVALID;
+    if (n == 0) return RNVP_OK;
+    const long long n4 = n / 4;
+    const auto kern = ad->ctl ? k_adam<true> : k_adam<false>;
+    kern<<<rnvp_grid(n4, 256, 8192), 256, 0, (hipStream_t)stream>>>(
+        (float4*)ad->param, (const float4*)ad->grad, (float4*)ad->exp_avg, (float4*)ad->exp_avg_sq, n4, ad->step,
+        ad->step_add, ad->lr, ad->beta1, ad->beta2, ad->eps, ad->weight_decay, (const uint32_t*)ad->mask,
+        ad->reg_coef, ad->ctl);
     RNVP_LAUNCH_CHECK();
     return RNVP_OK;
 }

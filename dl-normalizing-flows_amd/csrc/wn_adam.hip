@@ -72,7 +72,7 @@ __device__ __forceinline__ int find_blk(const rnvp_wn_desc* d, int n, int b) {
     return lo;
 }
 
-template <typename T, bool SLABS>
+template <typename T, bool SLABS, bool CTL>
 __global__ __launch_bounds__(WA_THREADS) __attribute__((amdgpu_waves_per_eu(WA_WPE, 8))) void k_wn_adam(const rnvp_wn_desc* __restrict__ descs, int n_desc,
                                                         rnvp_adam_args ad, int nblk, double* z0, long long n0,
                                                         double* z1, long long n1) {
@@ -83,10 +83,11 @@ __global__ __launch_bounds__(WA_THREADS) __attribute__((amdgpu_waves_per_eu(WA_W
         for (long long i = i0; i < n1; i += stride) z1[i] = 0.0;
         return;
     }
+    if (CTL && adam_skipped(ad.ctl)) return;   // a skipped step: only the ranges above are written
     extern __shared__ float tile[];
     __shared__ double red[8 * 4];
     __shared__ float scl[8];
-    __shared__ float coef[2];
+    __shared__ float coef[3];
     // logical block order: XCD x (hardware block b runs on XCD b % 8) owns a
     // contiguous run of row blocks
     const int nb = nblk, b = blockIdx.x;
@@ -101,12 +102,7 @@ __global__ __launch_bounds__(WA_THREADS) __attribute__((amdgpu_waves_per_eu(WA_W
     const int co = co0 + r;
     const bool live = r < nr;
     float* trow = tile + r * RP;
-    if (threadIdx.x == 0) {
-        const double t = (double)(ad.step[0] + ad.step_add);
-        const double bc1 = 1.0 - pow((double)ad.beta1, t), bc2 = 1.0 - pow((double)ad.beta2, t);
-        coef[0] = (float)(ad.lr / bc1);
-        coef[1] = (float)(1.0 / sqrt(bc2));
-    }
+    if (threadIdx.x == 0) adam_coef(ad.step, ad.step_add, ad.lr, ad.beta1, ad.beta2, CTL ? ad.ctl : nullptr, coef);
     const long long vrow = d.dv_off + (long long)co * kr;
     RNVP_GLOBAL float* pv = (RNVP_GLOBAL float*)ad.param + vrow;
     RNVP_GLOBAL float* gv = (RNVP_GLOBAL float*)ad.grad + vrow;
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(WA_THREADS) __attribute__((amdgpu_waves_per_eu(WA_W
         }
     }
     __syncthreads();
-    const float step_size = coef[0], inv_bc2s = coef[1];
+    const float step_size = coef[0], inv_bc2s = coef[1], gclip = CTL ? coef[2] : 1.0f;
     const float nrm = (d.g && live) ? ((const RNVP_GLOBAL float*)d.norm)[co] : 1.f;
     const float gold = (d.g && live) ? ((const RNVP_GLOBAL float*)d.g)[co] : 1.f;
     // ---- phase 1a: <dW, v> (weight-norm backward needs it before dv).
@@ -186,8 +182,8 @@ __global__ __launch_bounds__(WA_THREADS) __attribute__((amdgpu_waves_per_eu(WA_W
         const float proj = (float)(dot / ((double)nrm * nrm));
         auto elem = [&](int i, float p, float gin, float& m, float& v2, float dwv, float& g) {
             g = SLABS ? (d.g ? gs * fmaf(-proj, p, dwv) : dwv) : gin;
-            return adam_elem(p, g, m, v2, 1, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.reg_coef, step_size,
-                             inv_bc2s);
+            return adam_elem<CTL>(p, g, m, v2, 1, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.reg_coef, step_size,
+                             inv_bc2s, gclip);
         };
         auto lds_at = [&](int i) {
             const int ci = fdiv_small(i, rkk), tap = i - ci * kk;
@@ -293,8 +289,8 @@ __global__ __launch_bounds__(WA_THREADS) __attribute__((amdgpu_waves_per_eu(WA_W
                 const int f = K0 ? K0[o] : 1;
                 if (f) {
                     float m = M0[o], s = S0[o];
-                    gnew = adam_elem(gold, dg, m, s, f, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.reg_coef,
-                                     step_size, inv_bc2s);
+                    gnew = adam_elem<CTL>(gold, dg, m, s, f, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.reg_coef,
+                                     step_size, inv_bc2s, gclip);
                     P0[o] = gnew;
                     M0[o] = m;
                     S0[o] = s;
@@ -309,8 +305,8 @@ __global__ __launch_bounds__(WA_THREADS) __attribute__((amdgpu_waves_per_eu(WA_W
                 const int f = K0 ? K0[o] : 1;
                 if (f) {
                     float m = M0[o], s = S0[o];
-                    P0[o] = adam_elem(P0[o], db, m, s, f, ad.beta1, ad.beta2, ad.eps, ad.weight_decay,
-                                      ad.reg_coef, step_size, inv_bc2s);
+                    P0[o] = adam_elem<CTL>(P0[o], db, m, s, f, ad.beta1, ad.beta2, ad.eps, ad.weight_decay,
+                                      ad.reg_coef, step_size, inv_bc2s, gclip);
                     M0[o] = m;
                     S0[o] = s;
                 }
@@ -365,22 +361,19 @@ __global__ void k_zero_ranges(const rnvp_range* __restrict__ r) {
 }
 
 // leftover trainable elements (BatchNorm affines, coupling scales, ...)
+template <bool CTL>
 __global__ void k_adam_gather(rnvp_adam_args ad, const long long* __restrict__ idx, long long n) {
-    __shared__ float coef[2];
-    if (threadIdx.x == 0) {
-        const double t = (double)(ad.step[0] + ad.step_add);
-        const double bc1 = 1.0 - pow((double)ad.beta1, t), bc2 = 1.0 - pow((double)ad.beta2, t);
-        coef[0] = (float)(ad.lr / bc1);
-        coef[1] = (float)(1.0 / sqrt(bc2));
-    }
+    __shared__ float coef[3];
+    if (CTL && adam_skipped(ad.ctl)) return;
+    if (threadIdx.x == 0) adam_coef(ad.step, ad.step_add, ad.lr, ad.beta1, ad.beta2, CTL ? ad.ctl : nullptr, coef);
     __syncthreads();
     for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < n; q += (long long)gridDim.x * blockDim.x) {
         const long long o = idx[q];
         const int f = ad.mask ? ad.mask[o] : 1;
         if (!f) continue;
         float m = ad.exp_avg[o], s = ad.exp_avg_sq[o];
-        ad.param[o] = adam_elem(ad.param[o], ad.grad[o], m, s, f, ad.beta1, ad.beta2, ad.eps, ad.weight_decay,
-                                ad.reg_coef, coef[0], coef[1]);
+        ad.param[o] = adam_elem<CTL>(ad.param[o], ad.grad[o], m, s, f, ad.beta1, ad.beta2, ad.eps, ad.weight_decay,
+                                     ad.reg_coef, coef[0], coef[1], CTL ? coef[2] : 1.0f);
         ad.exp_avg[o] = m;
         ad.exp_avg_sq[o] = s;
     }
@@ -411,13 +404,20 @@ extern "C" int rnvp_weight_norm_bwd_adam(const rnvp_wn_desc* d, int n_desc, int 
     double* a0 = (double*)zero0;
     double* a1 = (double*)zero1;
     const long long c0 = zero0_bytes / 8, c1 = zero1_bytes / 8;
+    // a launch without a step control runs the instantiation without one
+#define WA_LAUNCH(T, SL)                                                                                      \
+    do {                                                                                                      \
+        if (ad->ctl) k_wn_adam<T, SL, true><<<grid, WA_THREADS, WA_LDS, s>>>(d, n_desc, *ad, total_blocks, a0, c0, a1, c1); \
+        else k_wn_adam<T, SL, false><<<grid, WA_THREADS, WA_LDS, s>>>(d, n_desc, *ad, total_blocks, a0, c0, a1, c1);        \
+    } while (0)
     if (dtype == RNVP_BF16) {
-        if (from_slabs) k_wn_adam<bf16_t, true><<<grid, WA_THREADS, WA_LDS, s>>>(d, n_desc, *ad, total_blocks, a0, c0, a1, c1);
-        else k_wn_adam<bf16_t, false><<<grid, WA_THREADS, WA_LDS, s>>>(d, n_desc, *ad, total_blocks, a0, c0, a1, c1);
+        if (from_slabs) WA_LAUNCH(bf16_t, true);
+        else WA_LAUNCH(bf16_t, false);
     } else {
-        if (from_slabs) k_wn_adam<float, true><<<grid, WA_THREADS, WA_LDS, s>>>(d, n_desc, *ad, total_blocks, a0, c0, a1, c1);
-        else k_wn_adam<float, false><<<grid, WA_THREADS, WA_LDS, s>>>(d, n_desc, *ad, total_blocks, a0, c0, a1, c1);
+        if (from_slabs) WA_LAUNCH(float, true);
+        else WA_LAUNCH(float, false);
     }
+#undef WA_LAUNCH
     RNVP_LAUNCH_CHECK();
     return RNVP_OK;
 }
@@ -426,7 +426,8 @@ extern "C" int rnvp_adam_gather(const rnvp_adam_args* ad, const long long* idx, 
     if (!ad || n < 0 || (n > 0 && !idx)) return RNVP_E_INVALID;
     if (!ad->param || !ad->grad || !ad->exp_avg || !ad->exp_avg_sq || !ad->step) return RNVP_E_INVALID;
     if (n == 0) return RNVP_OK;
-    k_adam_gather<<<rnvp_grid(n, 256, 1024), 256, 0, (hipStream_t)stream>>>(*ad, idx, n);
+    if (ad->ctl) k_adam_gather<true><<<rnvp_grid(n, 256, 1024), 256, 0, (hipStream_t)stream>>>(*ad, idx, n);
+    else k_adam_gather<false><<<rnvp_grid(n, 256, 1024), 256, 0, (hipStream_t)stream>>>(*ad, idx, n);
     RNVP_LAUNCH_CHECK();
     return RNVP_OK;
 }

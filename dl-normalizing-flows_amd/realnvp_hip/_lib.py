@@ -76,11 +76,22 @@ class Range(C.Structure):
     _fields_ = [("p", vp), ("bytes", i64)]
 
 
+RNVP_DECAY_NONE, RNVP_DECAY_EXP, RNVP_DECAY_COSINE = 0, 1, 2
+
+
+class StepCtl(C.Structure):
+    _fields_ = [("base_lr", f32), ("warmup_start", f32), ("warmup_steps", i64),
+                ("decay", i32), ("decay_rate", f64), ("decay_steps", i64),
+                ("max_norm", f32),
+                ("lr", f32), ("grad_scale", f32), ("grad_norm", f32), ("skip", i32),
+                ("n_clipped", i64), ("n_skipped", i64)]
+
+
 class AdamArgs(C.Structure):
     _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("mask", vp),
                 ("step", vp), ("step_add", i64),
                 ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32),
-                ("reg_coef", f32)]
+                ("reg_coef", f32), ("ctl", vp)]
 
 
 WGRAD_GROUP_MAX = 24
@@ -184,6 +195,11 @@ _SIGS = {
     "rnvp_adam_step": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, f32, vp]),
     "rnvp_adam_update": (i32, [vp, vp, vp, vp, i64, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp]),
     "rnvp_step_increment": (i32, [vp, vp]),
+    "rnvp_grad_sumsq_parts": (i32, [i64]),
+    "rnvp_grad_sumsq": (i32, [C.POINTER(AdamArgs), i64, vp, i32, vp]),
+    "rnvp_step_control": (i32, [vp, vp, vp, i32, vp]),
+    "rnvp_adam_range": (i32, [C.POINTER(AdamArgs), i64, vp]),
+    "rnvp_step_advance": (i32, [vp, vp, vp]),
     "rnvp_fill_f64": (i32, [vp, i64, f64, vp]),
     "rnvp_net_group_prepare": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "rnvp_net_group": (i32, [vp, i32, i32, i32, i32, i32, vp]),
@@ -202,14 +218,14 @@ class _Lib:
             fn.restype = res
             fn.argtypes = args
             raw = name in ("rnvp_version", "rnvp_struct_size", "rnvp_stat_shards", "rnvp_wgrad_slabs", "rnvp_wgrad_replicas",
-                           "rnvp_link_nclass", "rnvp_conv2d_check",
+                           "rnvp_link_nclass", "rnvp_conv2d_check", "rnvp_grad_sumsq_parts",
                            "rnvp_weight_norm_tiles", "rnvp_weight_norm_opt_blocks",
                            "rnvp_net_group_prepare") or res is not i32
             setattr(self, name[len("rnvp_"):], fn if raw else self._wrap(name, fn))
         # the struct mirrors must match the library's layouts (rnvp_struct_size): a
         # table read at another stride would address arbitrary device memory
         mirrors = (BNSrc, BNRunning, ConvArgs, WgradConv, WgradGroup, BNBwdArgs, WNDesc, AdamArgs, CouplingArgs,
-                   NetStep, Range, LinkArgs)
+                   NetStep, Range, LinkArgs, StepCtl)
         for i, m in enumerate(mirrors):
             if self.dll.rnvp_struct_size(i) != C.sizeof(m):
                 raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"

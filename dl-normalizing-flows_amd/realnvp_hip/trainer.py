@@ -20,6 +20,11 @@ MI355X-specific structure:
     stay per rank (= the reference's semantics for each 64-image shard).
   * optimizer state converts to / from torch.optim.Adam.state_dict() format
     (train.py:139-154, 249-250 checkpoints).
+  * optional step control (max_grad_norm / lr_schedule): the learning rate,
+    clip_grad_norm_'s scale and the refusal of a non-finite gradient are
+    decided on the device every step (rnvp_step_control), from a block the
+    host only writes with stream-ordered copies -- the captured graph follows
+    a schedule, set_lr() or set_max_grad_norm() without re-capture.
 """
 import ctypes as C
 import gc
@@ -98,7 +103,16 @@ def bucket_plan(model, bucket_elems, n_total):
 class FlowTrainer:
     def __init__(self, model, batch_size, lr=5e-4, weight_decay=5e-5, betas=(0.9, 0.999), eps=1e-8,
                  scale_reg=5e-5, dtype="bf16", seed=0, process_group=None, bucket_mb=25, overlap=False,
-                 comm="overlap", reduce_dtype="fp32", param_pass=None, chain=True):
+                 comm="overlap", reduce_dtype="fp32", param_pass=None, chain=True, max_grad_norm=None,
+                 lr_schedule=None):
+        from .stepctl import StepSchedule, check_max_grad_norm
+        if lr_schedule is not None and not isinstance(lr_schedule, StepSchedule):
+            raise ValueError("lr_schedule must be a realnvp_hip.stepctl.StepSchedule or None")
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.lr_schedule = lr_schedule
+        # gradient-norm clipping (and the non-finite skip) is part of the step's
+        # launch schedule: fixed at construction
+        self.clip = self.max_grad_norm is not None
         self.model = model
         self.dev = next(model.parameters()).device
         if self.dev.type != "cuda":
@@ -115,6 +129,7 @@ class FlowTrainer:
         model.set_precision(dtype)
         model.train()
         self._build_arenas()
+        self._build_step_control()
         self._build_plan(chain)
         self.graph = None
         self.graph_opt = None
@@ -142,6 +157,8 @@ class FlowTrainer:
         self._build_param_pass("separate" if param_pass == "separate" else "fused")
         if param_pass == "fused" and not self.fused:
             raise ValueError("param_pass='fused' is not possible for this model: %s" % self.param_pass_reason)
+        if self.ctl_buf is not None and not self.fused:
+            self._opt_all = self._adam_args(0)
         self._build_adam_ranges()
         self._build_buckets()
         self._cap_pg = self._capture_group()
@@ -172,6 +189,102 @@ class FlowTrainer:
         self.mask = torch.from_numpy(mask).to(dev)
         self.step_t = torch.zeros(1, device=dev, dtype=torch.int64)
         self.n_trainable = int((mask > 0).sum())
+
+    # ----------------------------------------------------------- step control
+    def _build_step_control(self):
+        """The device-resident rnvp_step_ctl block (include/realnvp_hip.h) of a
+        trainer built with lr_schedule and / or max_grad_norm, and the norm
+        reduction's partials.  The host writes its configuration fields with
+        stream-ordered fills (set_lr, set_max_grad_norm); nothing of it is a
+        captured launch argument but its address."""
+        self.ctl_buf = self.gs_partials = None
+        if self.lr_schedule is None and not self.clip:
+            return
+        from ._lib import StepCtl
+        from .engine import upload
+        from .stepctl import StepSchedule, fill_ctl
+        c = fill_ctl(StepCtl(), self.lr, self.lr_schedule, self.max_grad_norm)
+        c.lr = self.lr * (self.lr_schedule or StepSchedule()).factor(0)
+        c.grad_scale = 1.0
+        self.ctl_buf = upload(bytes(c), self.dev)
+        if self.clip:
+            self.gs_parts = int(_lib.lib().grad_sumsq_parts(self.n))
+            self.gs_partials = torch.zeros(self.gs_parts, device=self.dev, dtype=torch.float64)
+
+    def _ctl_field(self, name):
+        """a one-element tensor view of a field of the control block"""
+        from ._lib import StepCtl
+        f = getattr(StepCtl, name)
+        ct = dict(StepCtl._fields_)[name]
+        dt = {C.c_float: torch.float32, C.c_double: torch.float64, C.c_int: torch.int32, C.c_longlong: torch.int64}[ct]
+        return self.ctl_buf[f.offset:f.offset + f.size].view(dt)
+
+    def _write_ctl_config(self):
+        from ._lib import StepCtl
+        from .stepctl import fill_ctl
+        c = fill_ctl(StepCtl(), self.lr, self.lr_schedule, self.max_grad_norm)
+        for name in ("base_lr", "warmup_start", "warmup_steps", "decay", "decay_rate", "decay_steps", "max_norm"):
+            self._ctl_field(name).fill_(getattr(c, name))
+
+    def set_lr(self, lr):
+        """The base learning rate from the next step on.  With a control block
+        a stream-ordered write (no re-capture); without one the rate is a
+        captured launch argument, so the graph is dropped."""
+        self.lr = float(lr)
+        if self.ctl_buf is not None:
+            self._ctl_field("base_lr").fill_(self.lr)
+            return
+        self._refresh_adam_args()
+        if self.graph is not None:
+            self.drop_graph()
+
+    def set_max_grad_norm(self, v):
+        """The clipping threshold from the next step on (None: no clipping, the
+        non-finite skip stays); a stream-ordered write, no re-capture.  Needs a
+        trainer built with max_grad_norm: the norm pass is part of its step."""
+        from .stepctl import check_max_grad_norm
+        if not self.clip:
+            raise RuntimeError("set_max_grad_norm needs a FlowTrainer built with max_grad_norm (the gradient-norm "
+                               "pass is part of the step's launch schedule)")
+        self.max_grad_norm = check_max_grad_norm(v)
+        self._ctl_field("max_norm").fill_(self.max_grad_norm if self.max_grad_norm is not None else 0.0)
+
+    def step_control_state(self):
+        """What rnvp_step_control decided in the last step: lr, grad_norm (the
+        pre-clip norm), grad_scale, skip, and the counters n_clipped /
+        n_skipped.  Synchronises (a device-to-host copy): the one documented
+        sync of the step control."""
+        if self.ctl_buf is None:
+            raise RuntimeError("this FlowTrainer has no step control (built without lr_schedule / max_grad_norm)")
+        from ._lib import StepCtl
+        c = StepCtl.from_buffer_copy(bytes(self.ctl_buf.cpu().numpy()))
+        return {"lr": c.lr, "grad_norm": c.grad_norm, "grad_scale": c.grad_scale, "skip": int(c.skip),
+                "n_clipped": int(c.n_clipped), "n_skipped": int(c.n_skipped)}
+
+    def _open_step(self):
+        """first launch of a step with a control block: this step's learning
+        rate, no clip and no skip until the norm has been taken"""
+        if self.ctl_buf is not None:
+            _launch("param", 64, 0.0, _lib.lib().step_control, self.ctl_buf.data_ptr(), self.step_t.data_ptr(), None,
+                    0, stream_ptr())
+
+    def _grad_norm_control(self):
+        """Between the last gradient (after the all-reduce) and the first Adam
+        launch: the arena's sum of squares, then the clip scale / skip."""
+        if not self.clip:
+            return
+        L = _lib.lib()
+        s = stream_ptr()
+        _launch("param", 5 * self.n, 0.0, L.grad_sumsq, C.byref(self._opt_all), self.n, self.gs_partials.data_ptr(),
+                self.gs_parts, s)
+        _launch("param", 8 * self.gs_parts + 64, 0.0, L.step_control, self.ctl_buf.data_ptr(),
+                self.step_t.data_ptr(), self.gs_partials.data_ptr(), self.gs_parts, s)
+
+    def _advance_step(self):
+        if self.ctl_buf is not None:
+            _lib.lib().step_advance(self.step_t.data_ptr(), self.ctl_buf.data_ptr(), stream_ptr())
+        else:
+            _lib.lib().step_increment(self.step_t.data_ptr(), stream_ptr())
 
     # ------------------------------------------------------------------- plan
     def _build_plan(self, chain=True):
@@ -303,6 +416,7 @@ class FlowTrainer:
         parameters changed outside the trainer's own kernels (_packed_token).
         mode 'separate' keeps weight_norm_fwd + weight_norm_bwd + adam_step."""
         self.fused = False
+        self._slab_table = None
         self._packed_token = None
         self.param_pass_mode, self.param_pass_reason = "separate", "requested"
         if mode != "fused":
@@ -333,10 +447,13 @@ class FlowTrainer:
                 self.param_pass_reason = "a conv row of %s does not fit the fused pass's LDS" % self._module_name(
                     st[1])
                 return
-            if self.pg is None:
+            if self.pg is None and not self.clip:
                 # single process: every coupling's pass is deferred to ONE launch
                 # at the end of the backward over the couplings' (persistent)
-                # weight-gradient slabs
+                # weight-gradient slabs.  (With gradient-norm clipping the
+                # gradients must be final before the pass that consumes them:
+                # the data-parallel schedule, with the norm where the
+                # all-reduce is.)
                 sdescs, rg = eng.param_pass_info(sv, self.dtype)
                 slab_descs += [rebased(d, off, blk0) for d in sdescs]
                 ranges += rg
@@ -386,11 +503,12 @@ class FlowTrainer:
         a.mask, a.step, a.step_add = self.mask.data_ptr() + off, self.step_t.data_ptr(), 1
         a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
         a.weight_decay, a.reg_coef = self.wd, self.reg
+        a.ctl = self.ctl_buf.data_ptr() if self.ctl_buf is not None else None
         return a
 
     def _refresh_adam_args(self):
         """lr / betas / eps / weight decay changed (load_optimizer_state_dict)"""
-        if not self.fused:
+        if not self.fused and self.ctl_buf is None:
             return
         for a in (self._opt_all,):
             a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
@@ -430,7 +548,7 @@ class FlowTrainer:
         when its update runs.  Disabled (one update at the end) unless the
         backward visits couplings in descending arena offset."""
         self.adam_ranges = None
-        if self.pg is not None or not self.overlap or self.fused or self.links is not None:
+        if self.pg is not None or not self.overlap or self.fused or self.links is not None or self.clip:
             return
         blocks = [st[6] for st in self.stages if st[0] == "coupling"]
         base = self.grad.data_ptr()
@@ -644,7 +762,7 @@ class FlowTrainer:
                 if self.adam_ranges is not None:
                     lo, hi = self.adam_ranges[ci]
                     after = (lambda lo=lo, hi=hi: self._adam_range(lo, hi))
-                opt = "defer" if (self.fused and self.pg is None) else None
+                opt = "defer" if self._slab_table is not None else None
                 eng.backward(sv, self._g(z), None, self.g_lp, block, gx=self._g(x), side=self.side, after=after,
                              zero_at_end=True, opt=opt)
                 self._issue_buckets(ci, n_coupling)
@@ -671,7 +789,7 @@ class FlowTrainer:
         the previous coupling's link backward has read those sums; its
         all-reduce buckets follow them."""
         n_coupling = len(self.cidx)
-        opt = "defer" if (self.fused and self.pg is None) else None
+        opt = "defer" if self._slab_table is not None else None
         pending, pending_ci = [], None
         for k in reversed(range(n_coupling)):
             _, mod, eng, x, z, sv, block = self.stages[self.cidx[k]]
@@ -706,21 +824,24 @@ class FlowTrainer:
         b1, b2 = self.betas
         if hi <= lo:
             return
+        if self.ctl_buf is not None:
+            _lib.lib().adam_range(C.byref(self._adam_args(lo)), hi - lo, stream_ptr())
+            return
         _lib.lib().adam_update(self.param.data_ptr() + 4 * lo, self.grad.data_ptr() + 4 * lo,
                                self.exp_avg.data_ptr() + 4 * lo, self.exp_avg_sq.data_ptr() + 4 * lo, hi - lo,
                                self.step_t.data_ptr(), 1, self.lr, b1, b2, self.eps, self.wd,
                                self.mask.data_ptr() + lo, self.reg, stream_ptr())
 
     def _optimizer(self):
+        self._grad_norm_control()
         if self.fused:
-            from .engine import _launch
             L = _lib.lib()
             s = stream_ptr()
-            import ctypes as C
             dt = 1 if self.dtype == "bf16" else 0
             pb, tb = self._param_bytes
-            if self.pg is not None:
-                # data parallel: the conv rows' Adam + norms + images, after the all-reduce
+            if self._slab_table is None:
+                # data parallel (or gradient-norm clipping): the conv rows' Adam +
+                # norms + images, after the all-reduce (the norm)
                 t, n, nblk = self._opt_table
                 _launch("param", pb, 0.0, L.weight_norm_bwd_adam, t.data_ptr(), n, nblk, 0, dt,
                         C.byref(self._opt_all), None, 0, None, 0, s)
@@ -738,11 +859,16 @@ class FlowTrainer:
                 _launch("param", tb / len(self.wn_tables), 0.0, L.weight_norm_transpose, t.data_ptr(), n, tiles, dt,
                         s)
             L.adam_gather(C.byref(self._opt_all), self._opt_rest.data_ptr(), self._opt_rest.numel(), s)
-            L.step_increment(self.step_t.data_ptr(), s)
+            self._advance_step()
             return
         if self.adam_ranges is not None:
             # the per-coupling updates already ran (side stream, t = step + 1)
-            _lib.lib().step_increment(self.step_t.data_ptr(), stream_ptr())
+            self._advance_step()
+            return
+        if self.ctl_buf is not None:
+            # rnvp_adam_step's update (t = step + 1) under the step control
+            _lib.lib().adam_range(C.byref(self._opt_all), self.n, stream_ptr())
+            self._advance_step()
             return
         b1, b2 = self.betas
         _lib.lib().adam_step(self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
@@ -758,6 +884,7 @@ class FlowTrainer:
             self._reduce_bucket(lo, hi)
 
     def _fwd_bwd(self):
+        self._open_step()
         if self.fused:
             # every conv gradient (v, g, bias) is written, not accumulated, by
             # the row kernels and every BatchNorm affine gradient by its
@@ -782,12 +909,15 @@ class FlowTrainer:
     # --------------------------------------------------------------- graphs
     def _snapshot(self):
         bufs = {n: b.detach().clone() for n, b in self.model.named_buffers()}
+        ctl = self.ctl_buf.clone() if self.ctl_buf is not None else None
         return (self.param.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.step_t.clone(),
-                self.ll_acc.clone(), bufs)
+                self.ll_acc.clone(), bufs, ctl)
 
     def _restore(self, snap):
-        p, m, v, t, ll, bufs = snap
+        p, m, v, t, ll, bufs, ctl = snap
         with torch.no_grad():
+            if ctl is not None:
+                self.ctl_buf.copy_(ctl)     # the warm-up steps' counters
             self.param.copy_(p)
             self.exp_avg.copy_(m)
             self.exp_avg_sq.copy_(v)
@@ -973,8 +1103,14 @@ class FlowTrainer:
         if len(steps) > 1:
             raise ValueError("per-parameter Adam step counts differ: %s" % sorted(steps))
         self.step_t.fill_(int(steps.pop()) if steps else 0)
+        baked = (tuple(self.betas), self.eps, self.wd) != (tuple(g0["betas"]), g0["eps"], g0["weight_decay"])
         self.lr, self.betas, self.eps, self.wd = g0["lr"], tuple(g0["betas"]), g0["eps"], g0["weight_decay"]
         self._refresh_adam_args()
+        if self.ctl_buf is not None:
+            # the base rate lives in the control block: no re-capture for it
+            self._ctl_field("base_lr").fill_(self.lr)
+            if not baked:
+                return
         if self.graph is not None:
             self.drop_graph()    # lr / betas are baked into the captured launches
 
@@ -989,14 +1125,42 @@ class FlowTrainer:
     def state_dict(self):
         """{'model': model.state_dict(), 'optimizer': torch-Adam-format state,
         'rng': rng_state()} (the two files train.py:249-250 writes, plus the
-        noise stream so a resumed run draws the same noise as an unbroken one)."""
-        return {"model": self.model.state_dict(), "optimizer": self.optimizer_state_dict(),
-                "rng": self.rng_state()}
+        noise stream so a resumed run draws the same noise as an unbroken one).
+        A trainer with a step control adds 'step_control': the schedule's
+        configuration, max_grad_norm and the two counters (the base rate
+        stays in the optimizer's param_groups[0]['lr'])."""
+        sd = {"model": self.model.state_dict(), "optimizer": self.optimizer_state_dict(),
+              "rng": self.rng_state()}
+        if self.ctl_buf is not None:
+            st = self.step_control_state()
+            sd["step_control"] = {"schedule": self.lr_schedule.config() if self.lr_schedule is not None else None,
+                                  "max_grad_norm": self.max_grad_norm, "n_clipped": st["n_clipped"],
+                                  "n_skipped": st["n_skipped"]}
+        return sd
+
+    def _load_step_control(self, sc):
+        from .stepctl import StepSchedule, check_max_grad_norm
+        if self.ctl_buf is None:
+            if sc["schedule"] is not None or sc["max_grad_norm"] is not None:
+                raise ValueError("the checkpoint carries a step control (%r); build the FlowTrainer with "
+                                 "lr_schedule / max_grad_norm to resume it" % (sc,))
+            return
+        mgn = check_max_grad_norm(sc["max_grad_norm"])
+        if mgn is not None and not self.clip:
+            raise ValueError("the checkpoint clips at max_grad_norm=%g; build the FlowTrainer with max_grad_norm "
+                             "to resume it" % mgn)
+        self.lr_schedule = StepSchedule.from_config(sc["schedule"]) if sc["schedule"] is not None else None
+        self.max_grad_norm = mgn
+        self._write_ctl_config()
+        self._ctl_field("n_clipped").fill_(int(sc["n_clipped"]))
+        self._ctl_field("n_skipped").fill_(int(sc["n_skipped"]))
 
     def load_state_dict(self, sd):
         with torch.no_grad():
             self.model.load_state_dict(sd["model"])
         self.load_optimizer_state_dict(sd["optimizer"])
+        if sd.get("step_control") is not None:
+            self._load_step_control(sd["step_control"])
         rng = sd.get("rng")
         if rng is not None:
             # a checkpoint of THIS rank resumes its noise stream exactly; one

@@ -36,7 +36,7 @@ int rnvp_version(void);
 /* sizeof the library's argument structs, in this order: rnvp_bn_src,
  * rnvp_bn_running, rnvp_conv_args, rnvp_wgrad_conv, rnvp_wgrad_group,
  * rnvp_bn_bwd_args, rnvp_wn_desc, rnvp_adam_args, rnvp_coupling_args,
- * rnvp_net_step, rnvp_range, rnvp_link_args (-1 past the end).  A binding compares them with
+ * rnvp_net_step, rnvp_range, rnvp_link_args, rnvp_step_ctl (-1 past the end).  A binding compares them with
  * its own mirrors at load time: a library built from another header revision
  * is refused instead of reading descriptor tables at the wrong stride. */
 int rnvp_struct_size(int which);
@@ -280,10 +280,35 @@ int rnvp_weight_norm_bwd(const rnvp_wn_desc* descs_device, int n_desc, int total
  * descriptor of this call must have (the binding checks its tables).
  * zero0 / zero1 as rnvp_weight_norm_bwd.  Replaces modules_realnvp.py:53-59
  * (weight_norm) and train.py:134, 200 (Adam) for the s/t convs. */
+/* Device-resident step control (learning-rate schedule, gradient-norm
+ * clipping, non-finite skip; see "step control" below).  The host writes the
+ * configuration with stream-ordered copies -- it is never a captured launch
+ * argument, so a replayed HIP graph follows every change -- and
+ * rnvp_step_control writes the decisions the Adam kernels read. */
+enum { RNVP_DECAY_NONE = 0, RNVP_DECAY_EXP = 1, RNVP_DECAY_COSINE = 2 };
+typedef struct rnvp_step_ctl {
+    /* configuration, written by the host */
+    float base_lr; float warmup_start; long long warmup_steps;
+    int decay; double decay_rate; long long decay_steps;   /* fp64: r^u carries the rate's rounding u times */
+    float max_norm;                       /* <= 0: no clipping */
+    /* written by rnvp_step_control every step */
+    float lr, grad_scale, grad_norm; int skip;
+    long long n_clipped, n_skipped;
+} rnvp_step_ctl;
+/* ctl (optional, device): NULL = lr below, gradients as they are.  Non-NULL:
+ * the Adam kernels (rnvp_weight_norm_bwd_adam, rnvp_adam_gather,
+ * rnvp_adam_range) take the learning rate from ctl->lr instead of lr,
+ * multiply the incoming gradient (regulariser included, weight decay not) by
+ * ctl->grad_scale -- a scale of exactly 1.0f leaves every bit of the update as
+ * without ctl -- and touch no memory at all when ctl->skip is set (except
+ * rnvp_weight_norm_bwd_adam's zero0 / zero1 ranges, which are still zeroed;
+ * a skipped from_slabs = 1 pass leaves its slabs unconsumed: a caller that
+ * can skip runs rnvp_weight_norm_bwd first and passes from_slabs = 0). */
 typedef struct rnvp_adam_args {
     float* param; float* grad; float* exp_avg; float* exp_avg_sq; const uint8_t* mask;
     const long long* step; long long step_add;
     float lr, beta1, beta2, eps, weight_decay, reg_coef;
+    const rnvp_step_ctl* ctl;
 } rnvp_adam_args;
 int rnvp_weight_norm_opt_blocks(int cout, int cin, int ks);
 int rnvp_weight_norm_bwd_adam(const rnvp_wn_desc* descs_device, int n_desc, int total_blocks, int from_slabs,
@@ -483,6 +508,50 @@ int rnvp_adam_update(float* param, float* grad, float* exp_avg, float* exp_avg_s
                      const long long* step, long long step_add, float lr, float beta1, float beta2, float eps,
                      float weight_decay, const uint8_t* mask, float reg_coef, void* stream);
 int rnvp_step_increment(long long* step, void* stream);
+
+/* ---- step control --------------------------------------------------------
+ * Decisions taken on the device between the backward and the parameter pass,
+ * so that a captured step needs no re-capture for a learning-rate schedule
+ * and can bound or refuse its own update.  u = *step is the number of
+ * optimizer steps already taken; everything below is evaluated in fp64 and
+ * rounded once to fp32.
+ *   lr = base_lr * warm(u) * decay(u)
+ *   warm(u)  = s + (1 - s) min(u, W) / W  (s = warmup_start, W = warmup_steps;
+ *              1 when W == 0): torch's LinearLR(start_factor = s, total_iters = W)
+ *   decay(u) = 1 (RNVP_DECAY_NONE) | r^u (RNVP_DECAY_EXP, r = decay_rate:
+ *              ExponentialLR) | f + (1 - f)(1 + cos(pi min(u, T) / T)) / 2
+ *              (RNVP_DECAY_COSINE, f = decay_rate, T = decay_steps: the closed
+ *              form of CosineAnnealingLR with eta_min = f base_lr, held after T)
+ *   grad_norm  = sqrt(sum of the partials): the L2 norm of what p.grad holds
+ *              after loss.backward() in the reference loop (train.py:192-198),
+ *              i.e. with the 5e-5 * weight_scale regulariser's gradient on
+ *              mask-2 elements, without Adam's weight decay, frozen elements
+ *              (mask 0) and padding excluded
+ *   grad_scale = min(1, max_norm / (grad_norm + 1e-6)), exactly 1.0f when the
+ *              clip does not bind or max_norm <= 0 (torch.nn.utils.clip_grad_norm_)
+ *   skip = 1 and n_skipped += 1 when the sum of squares is not finite;
+ *              n_clipped += 1 when grad_scale < 1.
+ *
+ * rnvp_grad_sumsq_parts(n): the number of partials rnvp_grad_sumsq writes for
+ * an n-element arena (1 .. 2048).
+ * rnvp_grad_sumsq: partials[b] = sum over workgroup b's share of the elements
+ * with mask_i > 0 of (g_i + [mask_i == 2] 2 reg_coef p_i)^2 in fp64 (a NULL
+ * mask = all 1).  Reads ad->grad, ad->param, ad->mask, ad->reg_coef; n % 4 ==
+ * 0, grad / param 16-byte and mask 4-byte aligned; n_parts must equal
+ * rnvp_grad_sumsq_parts(n).  One plain store per workgroup, no atomics: the
+ * result is bitwise reproducible.
+ * rnvp_step_control (one workgroup): partials == NULL (n_parts ignored) sets
+ * lr, grad_scale = 1 and skip = 0 -- it opens a step; otherwise it also adds
+ * the partials in a fixed order and sets grad_norm, grad_scale, skip and the
+ * counters.  n_parts <= 2048.
+ * rnvp_adam_range: rnvp_adam_update over [ad->param, ad->param + n) with the
+ * arguments of ad, honouring ad->ctl.
+ * rnvp_step_advance: rnvp_step_increment unless ctl->skip. */
+int rnvp_grad_sumsq_parts(long long n);
+int rnvp_grad_sumsq(const rnvp_adam_args* ad, long long n, double* partials, int n_parts, void* stream);
+int rnvp_step_control(rnvp_step_ctl* ctl, const long long* step, const double* partials, int n_parts, void* stream);
+int rnvp_adam_range(const rnvp_adam_args* ad, long long n, void* stream);
+int rnvp_step_advance(long long* step, const rnvp_step_ctl* ctl, void* stream);
 
 /* ---- net steps ------------------------------------------------------------
  * One s/t-net step as a table entry (rnvp_net_group): a conv (rnvp_conv2d
