@@ -20,6 +20,7 @@ extern "C" int rnvp_bn_bwd_apply(const rnvp_bn_bwd_args* a, void* stream) {
     if (!a || !a->g || !a->x || !a->dx || !a->sums || a->M < 0 || a->C <= 0 || (a->cs & 7) || a->cs < a->C)
         return RNVP_E_INVALID;
     if (a->sum_shards < 1) return RNVP_E_INVALID;
+    if (a->bn.tab && (!a->bn.sums || !al16(a->bn.tab))) return RNVP_E_INVALID;   // a finalized table: train mode
     if (a->dtype != RNVP_F32 && a->dtype != RNVP_BF16) return RNVP_E_INVALID;
     if (!al16(a->g) || !al16(a->x) || !al16(a->dx) || (a->residual && !al16(a->residual))) return RNVP_E_INVALID;
     if (a->M == 0) return RNVP_OK;

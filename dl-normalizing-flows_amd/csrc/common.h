@@ -439,10 +439,121 @@ __device__ __forceinline__ void block_bn_finish_aff(const rnvp_bn_src& s, int C,
     __syncthreads();
 }
 
+// ---- finalized BN tables (rnvp_bn_src.tab: [C][4] fp32) --------------------
+// entry {mean, rstd | mean, rstd}: flavour 0 has mean = sum * (1 / count)
+// (tab_finish), flavour 1 mean = sum / count (every other reader); a reader
+// forms scale = gamma rstd and shift = beta - mean gamma rstd in fp32 from its
+// flavour, exactly as from its own shard reduction
+enum { BN_TAB_MUL = 0, BN_TAB_DIV = 1 };
+typedef float bn_f32x2 __attribute__((ext_vector_type(2)));
+struct BnEntry { float scale, shift, mean, rstd; };
+__device__ __forceinline__ BnEntry bn_entry(float mean, float rstd, float g, float b) {
+    return BnEntry{g * rstd, b - mean * g * rstd, mean, rstd};
+}
+// channel c's {mean, rstd} of a finalized table (c clamped into the table: no branch)
+__device__ __forceinline__ bn_f32x2 bn_tab_load(const float* tab, int C, int c, int flavour) {
+    return *(const bn_f32x2*)(tab + (long long)max(0, min(c, C - 1)) * 4 + 2 * flavour);
+}
+// padding channels (>= C) of an LDS table: scale = shift = 0, mean = 0, rstd = 1
+__device__ __forceinline__ void bn_entry_store(const BnEntry& e, bool valid, int i, float* scale, float* shift,
+                                               float* mean_out, float* rstd_out) {
+    scale[i] = valid ? e.scale : 0.f;
+    shift[i] = valid ? e.shift : 0.f;
+    if (mean_out) mean_out[i] = valid ? e.mean : 0.f;
+    if (rstd_out) rstd_out[i] = valid ? e.rstd : 1.f;
+}
+// LDS table of channels [c0, c0+nc) from the finalized table: one 8-byte
+// load per channel (+ the affine), no reduction, no fp64, ONE barrier
+// (block_bn_table's result)
+__device__ __forceinline__ void block_bn_load(const rnvp_bn_src& s, int C, int c0, int nc, float* scale, float* shift,
+                                              float* mean_out, float* rstd_out, int flavour = BN_TAB_DIV) {
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) {
+        const int c = max(0, min(c0 + i, C - 1));
+        const bn_f32x2 mr = bn_tab_load(s.tab, C, c, flavour);
+        const float g = s.gamma ? s.gamma[c] : 1.f, b = s.beta ? s.beta[c] : 0.f;
+        bn_entry_store(bn_entry(mr.x, mr.y, g, b), c0 + i < C, i, scale, shift, mean_out, rstd_out);
+    }
+    __syncthreads();
+}
+
+// The finalized-table form of shard_issue: thread i < nc loads channel
+// c0 + i's {mean, rstd} (flavour BN_TAB_DIV) into slot 0 of its ShardLoads --
+// registers the shard path would have used, so a kernel that takes either
+// path by a uniform branch holds no more -- and tabf_entry forms the entry
+// with the affine parameters of bn_aff_issue.  The 8 bytes travel as one
+// double's bit pattern (moves only).
+template <int U>
+__device__ __forceinline__ void tabf_issue(const float* tab, int C, int c0, int nc, ShardLoads<U>& L) {
+    const int i = (int)threadIdx.x < nc ? (int)threadIdx.x : 0;
+    L.v1[0] = *(const double*)(tab + (long long)max(0, min(c0 + i, C - 1)) * 4 + 2 * BN_TAB_DIV);
+}
+template <int U>
+__device__ __forceinline__ BnEntry tabf_entry(const ShardLoads<U>& L, const rnvp_bn_src& s, BnAff A) {
+    const unsigned long long a = (unsigned long long)__double_as_longlong(L.v1[0]);
+    return bn_entry(__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), s.gamma ? A.g : 1.f,
+                    s.beta ? A.b : 0.f);
+}
+// block_bn_finish_aff's result from tabf_issue's registers (nc <= blockDim.x);
+// NO barrier: the caller's next one publishes the table
+template <int U>
+__device__ __forceinline__ void tabf_finish(const ShardLoads<U>& L, const rnvp_bn_src& s, BnAff A, int C, int c0,
+                                            int nc, float* scale, float* shift, float* mean_out, float* rstd_out) {
+    const int i = threadIdx.x;
+    if (i < nc) bn_entry_store(tabf_entry(L, s, A), c0 + i < C, i, scale, shift, mean_out, rstd_out);
+}
+
+// The writer: one s/t-net BatchNorm site's running-statistics update (torch
+// BatchNorm2d train-mode semantics) and, when r.tab is set, its finalized
+// table, by one workgroup with the complete batch sums in hand.  tmp: 2*C
+// doubles of LDS.  Must be reached by every thread of the block.
+__device__ __forceinline__ void bn_running_site(const rnvp_bn_running& r, float mom, double* tmp) {
+    const int C = r.C;
+    // the shards added in shard order (what the register tables and
+    // shard_sum_tab add: the result does not depend on an atomic's turn), 8
+    // loads in flight at a time
+    const int ns = r.shards < 1 ? 1 : r.shards;
+    for (int c = threadIdx.x; c < 2 * C; c += blockDim.x) {
+        double acc = 0.0;
+        for (int h0 = 0; h0 < ns; h0 += 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = r.sums[(long long)min(h0 + u, ns - 1) * 2 * C + c];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (h0 + u < ns) acc += v[u];
+        }
+        tmp[c] = acc;
+    }
+    __syncthreads();
+    const double inv = 1.0 / r.count;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const double s1 = tmp[c], s2 = tmp[C + c];
+        const double mean = s1 / r.count;
+        double var = s2 / r.count - mean * mean;
+        if (var < 0) var = 0;
+        const double unb = r.count > 1 ? var * r.count / (r.count - 1) : var;
+        r.rmean[c] = (1.f - mom) * r.rmean[c] + mom * (float)mean;
+        r.rvar[c] = (1.f - mom) * r.rvar[c] + mom * (float)unb;
+        if (r.tab) {
+            const double m0 = s1 * inv;
+            double v0 = s2 * inv - m0 * m0;
+            if (v0 < 0) v0 = 0;
+            *(floatx4*)(r.tab + (long long)c * 4) =
+                floatx4{(float)m0, (float)(1.0 / sqrt(v0 + (double)r.eps)), (float)mean,
+                        (float)(1.0 / sqrt(var + (double)r.eps))};
+        }
+    }
+    if (threadIdx.x == 0 && r.nbt) r.nbt[0] += 1;
+}
+
 // Whole-block BN table (shard reduction + finish).  tmp: 2*nc doubles of LDS.
 // Must be reached by every thread of the block.
 __device__ __forceinline__ void block_bn_table(const rnvp_bn_src& s, int C, int c0, int nc, float* scale, float* shift,
                                                float* mean_out, float* rstd_out, double* tmp) {
+    if (s.tab) {
+        block_bn_load(s, C, c0, nc, scale, shift, mean_out, rstd_out);
+        return;
+    }
     const int nv = max(0, min(nc, C - c0));
     if (s.sums) block_shard_sums(s.sums, C, s.shards, c0, nv, tmp, tmp + nc);
     block_bn_finish(s, C, c0, nc, scale, shift, mean_out, rstd_out, tmp);

@@ -59,6 +59,10 @@ int conv_args_status(const rnvp_conv_args* a) {
     if ((a->kp & 63) || a->kp < a->ks * a->ks * a->cs_in) return RNVP_E_INVALID;
     if (!al16(a->x) || !al16(a->w)) return RNVP_E_INVALID;
     if (a->epi_relu_bn_bwd && !a->epi_x) return RNVP_E_INVALID;
+    // a finalized table stands for batch sums: 16-byte entries, train mode only
+    auto tab_bad = [](const rnvp_bn_src& s) { return s.tab && (!s.sums || !al16(s.tab)); };
+    if ((a->pro_bn_relu && tab_bad(a->pro)) || (a->epi_relu_bn_bwd && tab_bad(a->epi)) || (a->bp && tab_bad(a->bp_bn)))
+        return RNVP_E_INVALID;
     if ((long long)a->B * a->H * a->W >= (1ll << 31)) return RNVP_E_UNSUPPORTED;
     if (a->bp) {
         if (!a->bp_x || !al16(a->bp_x) || (a->bp_out && !al16(a->bp_out))) return RNVP_E_INVALID;
@@ -89,28 +93,39 @@ int bp_cfg_of(const rnvp_conv_args* a) {
     return -1;
 }
 
-int dispatch_conv(const rnvp_conv_args* a, hipStream_t s) {
+// dry: the routing's checks only, nothing launched; fam (optional): the
+// family that runs (RNVP_FAMILY_*) -- rnvp_conv2d_family asks the dispatch
+// itself.  Only the families with a dry launcher are told apart; the
+// dispatch has a family for every shape that passes the argument checks.
+int dispatch_conv(const rnvp_conv_args* a, hipStream_t s, bool dry, int* fam) {
+    auto ran = [&](int f, int r) {
+        if (fam && r == RNVP_OK) *fam = f;
+        return r;
+    };
     // forced deep-scale configuration (A/B and parity tests): no fallback
-    if (a->variant >= RNVP_VARIANT_DEEP0) return rnvp_deep_launch(a, s, a->variant - RNVP_VARIANT_DEEP0);
+    if (a->variant >= RNVP_VARIANT_DEEP0)
+        return ran(RNVP_FAMILY_DEEP, rnvp_deep_launch(a, s, a->variant - RNVP_VARIANT_DEEP0, dry));
     if (a->variant == 0 || a->variant == RNVP_VARIANT_DEEP) {
         const int cfg = rnvp_deep_auto_cfg(a);
         if (cfg >= 0) {
-            const int r = rnvp_deep_launch(a, s, cfg);
-            if (r != RNVP_E_UNSUPPORTED) return r;
+            const int r = rnvp_deep_launch(a, s, cfg, dry);
+            if (r != RNVP_E_UNSUPPORTED) return ran(RNVP_FAMILY_DEEP, r);
         }
     }
     const bool tuned = a->variant != 1;
     // bf16 1x1 convs of the wide scales: the register-pipelined stream kernel (conv_s1.hip)
     if (tuned && a->dtype == RNVP_BF16 && a->ks == 1) {
-        const int r = rnvp_conv_s1_launch(a, s);
-        if (r != RNVP_E_UNSUPPORTED) return r;
+        const int r = rnvp_conv_s1_launch(a, s, dry);
+        if (r != RNVP_E_UNSUPPORTED) return ran(RNVP_FAMILY_S1, r);
     }
     if (tuned && rnvp_conv_band_ok(a)) {
         // the persistent band kernel (conv_band.hip) where it applies
-        const int r = rnvp_conv_band2_launch(a, s);
-        if (r != RNVP_E_UNSUPPORTED) return r;
+        const int r = rnvp_conv_band2_launch(a, s, dry);
+        if (r != RNVP_E_UNSUPPORTED) return ran(RNVP_FAMILY_BAND, r);
+        if (dry) return ran(RNVP_FAMILY_OTHER, RNVP_OK);
         return rnvp_conv_band1_launch(a, s);
     }
+    if (dry) return ran(RNVP_FAMILY_OTHER, RNVP_OK);
     {
         const int r = rnvp_conv_stream_launch(a, s);
         if (r != RNVP_E_UNSUPPORTED) return r;
@@ -123,18 +138,27 @@ int dispatch_conv(const rnvp_conv_args* a, hipStream_t s) {
 }
 
 // the whole routing of a checked conv; dry: every check, nothing launched
-// (rnvp_conv2d_check)
-int route_conv(const rnvp_conv_args* a, hipStream_t s, bool dry) {
+// (rnvp_conv2d_check, rnvp_conv2d_family)
+int route_conv(const rnvp_conv_args* a, hipStream_t s, bool dry, int* fam = nullptr) {
     if (a->bp) {
         const int cfg = bp_cfg_of(a);
-        if (cfg >= 0) return rnvp_deep_launch(a, s, cfg, dry);
-        // the wide scales' streaming 1x1 and band 3x3 (bf16) have the prologue too
-        if (a->variant != 0) return RNVP_E_UNSUPPORTED;
-        const int r = rnvp_conv_s1_launch(a, s, dry);
-        return r != RNVP_E_UNSUPPORTED ? r : rnvp_conv_band2_launch(a, s, dry);
+        int r, f = RNVP_FAMILY_DEEP;
+        if (cfg >= 0) {
+            r = rnvp_deep_launch(a, s, cfg, dry);
+        } else {
+            // the wide scales' streaming 1x1 and band 3x3 (bf16) have the prologue too
+            if (a->variant != 0) return RNVP_E_UNSUPPORTED;
+            f = RNVP_FAMILY_S1;
+            r = rnvp_conv_s1_launch(a, s, dry);
+            if (r == RNVP_E_UNSUPPORTED) {
+                f = RNVP_FAMILY_BAND;
+                r = rnvp_conv_band2_launch(a, s, dry);
+            }
+        }
+        if (fam && r == RNVP_OK) *fam = f;
+        return r;
     }
-    if (dry) return RNVP_OK;   // the dispatch has a family for every shape that passes the checks
-    return dispatch_conv(a, s);
+    return dispatch_conv(a, s, dry, fam);
 }
 
 }  // namespace
@@ -143,6 +167,15 @@ extern "C" int rnvp_conv2d(const rnvp_conv_args* a, void* stream) {
     const int st = conv_args_status(a);
     if (st != RNVP_OK || a->B == 0) return st;
     return route_conv(a, (hipStream_t)stream, false);
+}
+
+// the family rnvp_conv2d(a) runs on, as the routing itself reports it (dry)
+extern "C" int rnvp_conv2d_family(const rnvp_conv_args* a) {
+    const int st = conv_args_status(a);
+    if (st != RNVP_OK) return st;
+    int fam = RNVP_FAMILY_OTHER;
+    const int r = route_conv(a, nullptr, true, &fam);
+    return r == RNVP_OK ? fam : r;
 }
 
 extern "C" int rnvp_conv2d_check(const rnvp_conv_args* a) {

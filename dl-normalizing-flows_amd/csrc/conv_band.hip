@@ -208,14 +208,23 @@ __global__ __launch_bounds__(512) void k_conv_band2(rnvp_conv_args a, int shards
     BAND_STAMP(0);
     ShardLoads<2> pro_l, epi_l;
     const int pnv = min(cs, a.cin);
-    const bool pro_pre = PRO && a.pro.sums && shard_fits(pnv, a.pro.shards, 2);
-    const bool epi_pre = epi_bn && a.epi.sums && shard_fits(min(NC, N), a.epi.shards, 2);
-    if (pro_pre) shard_issue<2>(a.pro.sums, a.cin, a.pro.shards, 0, pnv, pro_l);
-    if (epi_pre) shard_issue<2>(a.epi.sums, N, a.epi.shards, 0, min(NC, N), epi_l);
+    // (a source with a finalized table, rnvp_bn_src.tab: its {mean, rstd} in
+    // the same registers, nothing to reduce)
+    const bool pro_pre = PRO && a.pro.sums && (a.pro.tab || shard_fits(pnv, a.pro.shards, 2));
+    const bool epi_pre = epi_bn && a.epi.sums && (a.epi.tab || shard_fits(min(NC, N), a.epi.shards, 2));
+    if (pro_pre) {
+        if (a.pro.tab) tabf_issue<2>(a.pro.tab, a.cin, 0, pnv, pro_l);
+        else shard_issue<2>(a.pro.sums, a.cin, a.pro.shards, 0, pnv, pro_l);
+    }
+    if (epi_pre) {
+        if (a.epi.tab) tabf_issue<2>(a.epi.tab, N, 0, min(NC, N), epi_l);
+        else shard_issue<2>(a.epi.sums, N, a.epi.shards, 0, min(NC, N), epi_l);
+    }
     // BP: the BatchNorm's statistics and the gradient sums (launcher: both fit shard_issue<2>)
     ShardLoads<BP ? 2 : 1> bpb_l, bpg_l;
     if constexpr (BP) {
-        shard_issue<2>(a.bp_bn.sums, a.cin, a.bp_bn.shards, 0, pnv, bpb_l);
+        if (a.bp_bn.tab) tabf_issue<2>(a.bp_bn.tab, a.cin, 0, pnv, bpb_l);
+        else shard_issue<2>(a.bp_bn.sums, a.cin, a.bp_bn.shards, 0, pnv, bpb_l);
         shard_issue<2>(a.bp_sums, a.cin, a.bp_shards, 0, pnv, bpg_l);
     }
     const BnAff bp_a = BP ? bn_aff_issue(a.bp_bn, a.cin, 0, a.w) : BnAff{1.f, 0.f};
@@ -238,7 +247,9 @@ __global__ __launch_bounds__(512) void k_conv_band2(rnvp_conv_args a, int shards
         if (!ok) wv[u] = u32x4{0u, 0u, 0u, 0u};
     }
     if (PRO) {
-        if (pro_pre) {
+        if (pro_pre && a.pro.tab) {
+            tabf_finish<2>(pro_l, a.pro, pro_a, a.cin, 0, cs, bnp, bnp + cs, nullptr, nullptr);   // (published by the barrier below)
+        } else if (pro_pre) {
             shard_finish<2>(pro_l, cs, tmp, tmp + cs);   // channels >= pnv stay zero (block_bn_finish pads them)
             block_bn_finish_aff(a.pro, a.cin, 0, cs, bnp, bnp + cs, nullptr, nullptr, tmp, pro_a);
         } else {
@@ -246,7 +257,9 @@ __global__ __launch_bounds__(512) void k_conv_band2(rnvp_conv_args a, int shards
         }
     }
     if (epi_bn) {
-        if (epi_pre) {
+        if (epi_pre && a.epi.tab) {
+            tabf_finish<2>(epi_l, a.epi, epi_a, N, 0, NC, etab, etab + NC, etab + 2 * NC, etab + 3 * NC);
+        } else if (epi_pre) {
             shard_finish<2>(epi_l, NC, tmp, tmp + NC);
             block_bn_finish_aff(a.epi, N, 0, NC, etab, etab + NC, etab + 2 * NC, etab + 3 * NC, tmp, epi_a);
         } else {
@@ -257,20 +270,30 @@ __global__ __launch_bounds__(512) void k_conv_band2(rnvp_conv_args a, int shards
         // A | B -> bnp, C -> the table scratch (read by stage_store): dL/dt =
         // A g - (B t + C), A = gamma rstd, B = A rstd k2, C = A (k1 - rstd k2 mean)
         double* gsm = red;                       // [2][cs] gradient sums (red is free until the statistics)
-        shard_finish<2>(bpb_l, cs, tmp, tmp + cs);
+        const bool bn_tabled = a.bp_bn.tab != nullptr;   // the BatchNorm's finalized entry: only the gradient sums are reduced
+        if (!bn_tabled) shard_finish<2>(bpb_l, cs, tmp, tmp + cs);
         shard_finish<2>(bpg_l, cs, gsm, gsm + cs);
         float A = 0.f, Bc = 0.f, Cc = 0.f;
         if (tid < pnv) {
             const double cnt = a.bp_bn.count, g1 = gsm[tid], g2 = gsm[cs + tid];
-            const double mean = tmp[tid] / cnt;
-            double var = tmp[cs + tid] / cnt - mean * mean;
-            if (var < 0) var = 0;
-            const float rstd = (float)(1.0 / sqrt(var + (double)a.bp_bn.eps));
-            A = (a.bp_bn.gamma ? bp_a.g : 1.f) * rstd;
+            float rstd, meanf;
+            if (bn_tabled) {
+                const BnEntry e = tabf_entry(bpb_l, a.bp_bn, bp_a);
+                A = e.scale;
+                meanf = e.mean;
+                rstd = e.rstd;
+            } else {
+                const double mean = tmp[tid] / cnt;
+                double var = tmp[cs + tid] / cnt - mean * mean;
+                if (var < 0) var = 0;
+                rstd = (float)(1.0 / sqrt(var + (double)a.bp_bn.eps));
+                A = (a.bp_bn.gamma ? bp_a.g : 1.f) * rstd;
+                meanf = (float)mean;
+            }
             const float k1 = (float)(g1 / cnt), k2 = (float)(g2 / cnt);
             const double rk2 = (double)rstd * (double)k2;
             Bc = (float)((double)A * rk2);
-            Cc = (float)((double)A * ((double)k1 - rk2 * (double)(float)mean));
+            Cc = (float)((double)A * ((double)k1 - rk2 * (double)meanf));
             if (blockIdx.x == 0) {
                 if (a.bp_dbeta) a.bp_dbeta[tid] = (float)g1;
                 if (a.bp_dgamma) a.bp_dgamma[tid] = (float)g2;

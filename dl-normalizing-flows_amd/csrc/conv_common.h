@@ -187,7 +187,9 @@ __host__ __device__ constexpr int halo_pitch(int cs) { return lds_mfma_pitch(cs,
 // BN table for channels [c0, c0+nc) of a source with <= 2 stat shards, in
 // registers (CPT channels per thread of NT, no LDS atomics): tab_issue loads
 // (unconditional, clamped addresses, so the loads can stay in flight behind
-// later ones), tab_finish forms scale/shift (+ mean, rstd) into LDS.
+// later ones), tab_finish forms scale/shift (+ mean, rstd) into LDS.  A source
+// with a finalized table (rnvp_bn_src.tab) loads its {mean, rstd} instead: no
+// shard sums, no fp64 arithmetic.
 template <int CPT>
 struct BnTab {
     double a1[CPT], a2[CPT], b1[CPT], b2[CPT];
@@ -200,7 +202,10 @@ __device__ __forceinline__ void tab_issue(const rnvp_bn_src& s, int C, int c0, i
     for (int j = 0; j < CPT; ++j) {
         const int c = threadIdx.x + NT * j;
         const int cc = (c < nc && c0 + c < C) ? c0 + c : 0;
-        if (s.sums) {
+        if (s.tab) {   // uniform: the finalized {mean, rstd} (8 B, as one double's bits), flavour BN_TAB_MUL
+            t.a1[j] = *(const double*)(s.tab + (long long)cc * 4);
+            t.a2[j] = t.b1[j] = t.b2[j] = 0.0;
+        } else if (s.sums) {
             t.a1[j] = s.sums[cc];
             t.a2[j] = s.sums[C + cc];
             if (s.shards > 1) {   // uniform: the second shard's loads only when it exists
@@ -228,7 +233,15 @@ __device__ __forceinline__ void tab_finish(const rnvp_bn_src& s, int C, int c0, 
         const int c = threadIdx.x + NT * j;
         if (c >= nc) continue;
         float sc = 0.f, sf = 0.f, mo = 0.f, ro = 1.f;
-        if (c0 + c < C) {
+        if (s.tab) {
+            if (c0 + c < C) {
+                const unsigned long long u = (unsigned long long)__double_as_longlong(t.a1[j]);
+                mo = __uint_as_float((unsigned)u);
+                ro = __uint_as_float((unsigned)(u >> 32));
+                sc = t.gam[j] * ro;
+                sf = t.bet[j] - mo * t.gam[j] * ro;
+            }
+        } else if (c0 + c < C) {
             double mean, var;
             if (s.sums) {
                 const double s1 = t.a1[j] + (s.shards > 1 ? t.b1[j] : 0.0);
@@ -286,6 +299,14 @@ __device__ __forceinline__ void bn_bwd_run(const rnvp_bn_bwd_args& a, double* ds
 #pragma unroll
         for (int j = 0; j < 2; ++j) gpre[j] = a.bn.gamma[min((int)threadIdx.x + j * (int)blockDim.x, C - 1)];
     }
+    // a finalized forward table (rnvp_bn_src.tab): the entries of the same two
+    // channels instead, and only the gradient sums are reduced below
+    const bool btab = a.bn.tab != nullptr;
+    bn_f32x2 epre[2] = {};
+    if (btab) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) epre[j] = bn_tab_load(a.bn.tab, C, threadIdx.x + j * blockDim.x, BN_TAB_DIV);
+    }
     // the thread's first data chunk is loaded before the statistic tables, so
     // its latency overlaps theirs instead of following the reduction (at the
     // deep scales that is every chunk of the thread); the optional operands
@@ -303,14 +324,14 @@ __device__ __forceinline__ void bn_bwd_run(const rnvp_bn_bwd_args& a, double* ds
     // both shard reductions (forward BN stats, backward g-sums): every load
     // issued up front, without branches, when the tables fit one pass
     // (ShardLoads); otherwise the looping block reduction
-    const bool two = a.bn.sums != nullptr;
+    const bool two = a.bn.sums != nullptr && !btab;
     if (shard_fits(C, a.sum_shards, 4) && shard_fits(C, two ? a.bn.shards : 1, 4)) {
         ShardLoads<4> lg, lb;
         shard_issue<4>(a.sums, C, a.sum_shards, 0, C, lg);
-        shard_issue<4>(two ? a.bn.sums : a.sums, C, two ? a.bn.shards : a.sum_shards, 0, C, lb);
+        if (!btab) shard_issue<4>(two ? a.bn.sums : a.sums, C, two ? a.bn.shards : a.sum_shards, 0, C, lb);
         for (int i = threadIdx.x; i < C; i += blockDim.x) {
             gs[i] = gs[cs + i] = 0.0;
-            dsm[i] = dsm[cs + i] = 0.0;
+            if (!btab) dsm[i] = dsm[cs + i] = 0.0;
         }
         __syncthreads();
 #pragma unroll
@@ -333,21 +354,27 @@ __device__ __forceinline__ void bn_bwd_run(const rnvp_bn_bwd_args& a, double* ds
         const ShardSrc src[1] = {{a.sums, C, a.sum_shards, 0, C, gs, gs + cs}};
         block_shard_sums_n<1>(src);
     }
-    auto entry = [&](int c, float gam) {
+    auto entry = [&](int c, float gam, const bn_f32x2& e) {
         float coef = 0.f, k1 = 0.f, k2 = 0.f, mean = 0.f, rstd = 1.f;
         if (c < C) {
-            double mn, var;
-            if (a.bn.sums) {
-                mn = dsm[c] / a.bn.count;
-                var = dsm[cs + c] / a.bn.count - mn * mn;
-                if (var < 0) var = 0;
+            if (btab) {
+                mean = e.x;
+                rstd = e.y;
+                coef = gam * rstd;
             } else {
-                mn = a.bn.mean[c];
-                var = a.bn.var[c];
+                double mn, var;
+                if (a.bn.sums) {
+                    mn = dsm[c] / a.bn.count;
+                    var = dsm[cs + c] / a.bn.count - mn * mn;
+                    if (var < 0) var = 0;
+                } else {
+                    mn = a.bn.mean[c];
+                    var = a.bn.var[c];
+                }
+                rstd = (float)(1.0 / sqrt(var + (double)a.bn.eps));
+                mean = (float)mn;
+                coef = gam * rstd;
             }
-            rstd = (float)(1.0 / sqrt(var + (double)a.bn.eps));
-            mean = (float)mn;
-            coef = gam * rstd;
             const double g1 = gs[c], g2 = gs[cs + c];
             if (a.bn.sums) {   // train mode: batch statistics carry gradient
                 k1 = (float)(g1 / cnt);
@@ -363,9 +390,10 @@ __device__ __forceinline__ void bn_bwd_run(const rnvp_bn_bwd_args& a, double* ds
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = threadIdx.x + j * blockDim.x;
-        if (c < cs) entry(c, gpre[j]);
+        if (c < cs) entry(c, gpre[j], epre[j]);
     }
-    for (int c = threadIdx.x + 2 * blockDim.x; c < cs; c += blockDim.x) entry(c, GAM ? a.bn.gamma[c] : 1.f);
+    for (int c = threadIdx.x + 2 * blockDim.x; c < cs; c += blockDim.x)
+        entry(c, (GAM && c < C) ? a.bn.gamma[c] : 1.f, btab ? bn_tab_load(a.bn.tab, C, c, BN_TAB_DIV) : bn_f32x2{});
     __syncthreads();
     // the grid stride is a multiple of the chunks per pixel in practice: the
     // channel chunk of a thread is then fixed (no 64-bit modulo per chunk)
@@ -444,6 +472,7 @@ int rnvp_deep_auto_cfg(const rnvp_conv_args* a);
 // tap-shared bf16 weight gradients (wgrad_tap.hip): RNVP_E_UNSUPPORTED when a
 // conv of the group is outside its staging limits (the caller falls back)
 int rnvp_wgrad_tap_launch(rnvp_wgrad_group* g, hipStream_t s);
+int rnvp_wgrad_tap_prepare(rnvp_wgrad_group* g);   // its checks and the convs' class fields, nothing launched
 
 // register-pipelined streaming 1x1 conv (conv_s1.hip): RNVP_E_UNSUPPORTED
 // outside bf16 / 1x1 / <= 64 channels / M >= 16k; dry: checks only

@@ -226,7 +226,10 @@ __device__ __forceinline__ void deep_tile(const rnvp_conv_args& a, int shards, i
         gsrc.sums = a.bp_sums;
         gsrc.count = a.bp_bn.count;
         gsrc.shards = a.bp_shards;
-        tab_issue<CPT, NT>(a.bp_bn, a.cin, 0, cs, btb);
+        // (a finalized table: the divide flavour, the fold's own rounding)
+        rnvp_bn_src bsrc = a.bp_bn;
+        if (bsrc.tab) bsrc.tab += 2 * BN_TAB_DIV;
+        tab_issue<CPT, NT>(bsrc, a.cin, 0, cs, btb);
         tab_issue<CPT, NT>(gsrc, a.cin, 0, cs, gtb);
     }
     if (epi_bn) tab_issue<1, NT>(a.epi, N, n0, BN, etb);
@@ -274,20 +277,27 @@ __device__ __forceinline__ void deep_tile(const rnvp_conv_args& a, int shards, i
             if (c >= cs) continue;
             float coef = 0.f, k1 = 0.f, k2 = 0.f, mo = 0.f, ro = 1.f;
             if (c < a.cin) {
-                double mean, var;
-                if (a.bp_bn.sums) {
-                    const double s1 = btb.a1[j] + (a.bp_bn.shards > 1 ? btb.b1[j] : 0.0);
-                    const double s2 = btb.a2[j] + (a.bp_bn.shards > 1 ? btb.b2[j] : 0.0);
-                    mean = s1 / a.bp_bn.count;   // (rnvp_bn_bwd_apply's rounding)
-                    var = s2 / a.bp_bn.count - mean * mean;
-                    if (var < 0) var = 0;
+                if (a.bp_bn.tab) {   // the finalized {mean, rstd}
+                    const unsigned long long u = (unsigned long long)__double_as_longlong(btb.a1[j]);
+                    mo = __uint_as_float((unsigned)u);
+                    ro = __uint_as_float((unsigned)(u >> 32));
+                    coef = btb.gam[j] * ro;
                 } else {
-                    mean = btb.a1[j];
-                    var = btb.a2[j];
+                    double mean, var;
+                    if (a.bp_bn.sums) {
+                        const double s1 = btb.a1[j] + (a.bp_bn.shards > 1 ? btb.b1[j] : 0.0);
+                        const double s2 = btb.a2[j] + (a.bp_bn.shards > 1 ? btb.b2[j] : 0.0);
+                        mean = s1 / a.bp_bn.count;   // (rnvp_bn_bwd_apply's rounding)
+                        var = s2 / a.bp_bn.count - mean * mean;
+                        if (var < 0) var = 0;
+                    } else {
+                        mean = btb.a1[j];
+                        var = btb.a2[j];
+                    }
+                    ro = (float)(1.0 / sqrt(var + (double)a.bp_bn.eps));
+                    mo = (float)mean;
+                    coef = btb.gam[j] * ro;
                 }
-                ro = (float)(1.0 / sqrt(var + (double)a.bp_bn.eps));
-                mo = (float)mean;
-                coef = btb.gam[j] * ro;
                 const double g1 = gtb.a1[j] + (a.bp_shards > 1 ? gtb.b1[j] : 0.0);
                 const double g2 = gtb.a2[j] + (a.bp_shards > 1 ? gtb.b2[j] : 0.0);
                 if (a.bp_bn.sums) {   // train mode: batch statistics carry gradient

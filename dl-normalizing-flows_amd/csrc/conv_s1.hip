@@ -73,11 +73,20 @@ __global__ __launch_bounds__(256, (s1_min_blocks<NT, NKS, NOPS>())) void k_conv_
     const int pnv = min(cs, a.cin);
     const bool pro_pre = TP && pro;
     const bool epi_pre = TP && epi_bn;
-    if (pro_pre) shard_issue<4>(a.pro.sums, a.cin, a.pro.shards, 0, pnv, pro_l);
-    if (epi_pre) shard_issue<4>(a.epi.sums, N, a.epi.shards, 0, min(NC, N), epi_l);
+    // (a source with a finalized table, rnvp_bn_src.tab: its {mean, rstd} per
+    // thread in the shard loads' registers -- a uniform branch, nothing to sum)
+    if (pro_pre) {
+        if (a.pro.tab) tabf_issue<4>(a.pro.tab, a.cin, 0, pnv, pro_l);
+        else shard_issue<4>(a.pro.sums, a.cin, a.pro.shards, 0, pnv, pro_l);
+    }
+    if (epi_pre) {
+        if (a.epi.tab) tabf_issue<4>(a.epi.tab, N, 0, min(NC, N), epi_l);
+        else shard_issue<4>(a.epi.sums, N, a.epi.shards, 0, min(NC, N), epi_l);
+    }
     ShardLoads<BP ? 4 : 1> bpb_l, bpg_l;
     if constexpr (BP) {
-        shard_issue<4>(a.bp_bn.sums, a.cin, a.bp_bn.shards, 0, pnv, bpb_l);
+        if (a.bp_bn.tab) tabf_issue<4>(a.bp_bn.tab, a.cin, 0, pnv, bpb_l);
+        else shard_issue<4>(a.bp_bn.sums, a.cin, a.bp_bn.shards, 0, pnv, bpb_l);
         shard_issue<4>(a.bp_sums, a.cin, a.bp_shards, 0, pnv, bpg_l);
     }
     const BnAff bp_a = BP ? bn_aff_issue(a.bp_bn, a.cin, 0, a.w) : BnAff{1.f, 0.f};
@@ -277,23 +286,38 @@ __global__ __launch_bounds__(256, (s1_min_blocks<NT, NKS, NOPS>())) void k_conv_
     if constexpr (BP) {
         // dL/dt = A g - (B t + C): A = gamma rstd, B = A rstd k2, C = A (k1 - rstd k2 mean)
         // (rnvp_bn_bwd_apply's A (g - k1 - (t - mean) rstd k2) regrouped)
-        shard_sum_tab<4>(bpb_l, pnv, a.bp_bn.shards, tabred, tmp, tmp + cs);
-        const double S1 = tid < pnv ? tmp[tid] : 0.0, S2 = tid < pnv ? tmp[cs + tid] : 0.0;
-        __syncthreads();
+        // (the BatchNorm's finalized entry when it has one: only the gradient sums are reduced)
+        const bool btab = a.bp_bn.tab != nullptr;
+        double S1 = 0.0, S2 = 0.0;
+        if (!btab) {
+            shard_sum_tab<4>(bpb_l, pnv, a.bp_bn.shards, tabred, tmp, tmp + cs);
+            S1 = tid < pnv ? tmp[tid] : 0.0;
+            S2 = tid < pnv ? tmp[cs + tid] : 0.0;
+            __syncthreads();
+        }
         shard_sum_tab<4>(bpg_l, pnv, a.bp_shards, tabred, tmp, tmp + cs);
         if (tid < cs) {
             float A = 0.f, Bc = 0.f, Cc = 0.f;
             if (tid < pnv) {
                 const double g1 = tmp[tid], g2 = tmp[cs + tid], cnt = a.bp_bn.count;
-                const double mean = S1 / cnt;
-                double var = S2 / cnt - mean * mean;
-                if (var < 0) var = 0;
-                const float rstd = (float)(1.0 / sqrt(var + (double)a.bp_bn.eps));
-                A = (a.bp_bn.gamma ? bp_a.g : 1.f) * rstd;
+                float rstd, meanf;
+                if (btab) {
+                    const BnEntry e = tabf_entry(bpb_l, a.bp_bn, bp_a);
+                    A = e.scale;
+                    meanf = e.mean;
+                    rstd = e.rstd;
+                } else {
+                    const double mean = S1 / cnt;
+                    double var = S2 / cnt - mean * mean;
+                    if (var < 0) var = 0;
+                    rstd = (float)(1.0 / sqrt(var + (double)a.bp_bn.eps));
+                    A = (a.bp_bn.gamma ? bp_a.g : 1.f) * rstd;
+                    meanf = (float)mean;
+                }
                 const float k1 = (float)(g1 / cnt), k2 = (float)(g2 / cnt);
                 const double rk2 = (double)rstd * (double)k2;
                 Bc = (float)((double)A * rk2);
-                Cc = (float)((double)A * ((double)k1 - rk2 * (double)(float)mean));
+                Cc = (float)((double)A * ((double)k1 - rk2 * (double)meanf));
                 if (blockIdx.x == 0) {
                     if (a.bp_dbeta) a.bp_dbeta[tid] = (float)g1;
                     if (a.bp_dgamma) a.bp_dgamma[tid] = (float)g2;
@@ -307,12 +331,20 @@ __global__ __launch_bounds__(256, (s1_min_blocks<NT, NKS, NOPS>())) void k_conv_
     }
     if constexpr (TP) {
         if (pro) {
-            shard_sum_tab<4>(pro_l, pnv, a.pro.shards, tabred, tmp, tmp + cs);
-            block_bn_finish_aff(a.pro, a.cin, 0, cs, bnp, bnp + 64, nullptr, nullptr, tmp, pro_a);
+            if (a.pro.tab) {
+                tabf_finish<4>(pro_l, a.pro, pro_a, a.cin, 0, cs, bnp, bnp + 64, nullptr, nullptr);
+            } else {
+                shard_sum_tab<4>(pro_l, pnv, a.pro.shards, tabred, tmp, tmp + cs);
+                block_bn_finish_aff(a.pro, a.cin, 0, cs, bnp, bnp + 64, nullptr, nullptr, tmp, pro_a);
+            }
         }
         if (epi_bn) {
-            shard_sum_tab<4>(epi_l, min(NC, N), a.epi.shards, tabred, tmp, tmp + NC);
-            block_bn_finish_aff(a.epi, N, 0, NC, etab, etab + NC, etab + 2 * NC, etab + 3 * NC, tmp, epi_a);
+            if (a.epi.tab) {
+                tabf_finish<4>(epi_l, a.epi, epi_a, N, 0, NC, etab, etab + NC, etab + 2 * NC, etab + 3 * NC);
+            } else {
+                shard_sum_tab<4>(epi_l, min(NC, N), a.epi.shards, tabred, tmp, tmp + NC);
+                block_bn_finish_aff(a.epi, N, 0, NC, etab, etab + NC, etab + 2 * NC, etab + 3 * NC, tmp, epi_a);
+            }
         }
     } else {
         if (pro) block_bn_table(a.pro, a.cin, 0, cs, bnp, bnp + 64, nullptr, nullptr, tmp);

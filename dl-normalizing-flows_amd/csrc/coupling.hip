@@ -215,18 +215,7 @@ __global__ void k_out2(rnvp_coupling_args a, int main_grid) {
         // extra workgroups: one s/t-net BatchNorm running-stat update each
         // (the net's batch sums are complete: every conv ran before this launch)
         const rnvp_bn_running r = a.net_running[blockIdx.x - main_grid];
-        double* tmp = (double*)sh;   // [2*C]
-        block_shard_sums(r.sums, r.C, r.shards, 0, r.C, tmp, tmp + r.C);
-        const float mom = a.momentum;
-        for (int c = threadIdx.x; c < r.C; c += blockDim.x) {
-            double mean = tmp[c] / r.count;
-            double var = tmp[r.C + c] / r.count - mean * mean;
-            if (var < 0) var = 0;
-            double unb = r.count > 1 ? var * r.count / (r.count - 1) : var;
-            r.rmean[c] = (1.f - mom) * r.rmean[c] + mom * (float)mean;
-            r.rvar[c] = (1.f - mom) * r.rvar[c] + mom * (float)unb;
-        }
-        if (threadIdx.x == 0 && r.nbt) r.nbt[0] += 1;
+        bn_running_site(r, a.momentum, (double*)sh /* [2*C] */);
         return;
     }
     const Geo g = geo(a);

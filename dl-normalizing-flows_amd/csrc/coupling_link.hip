@@ -223,17 +223,7 @@ __device__ __forceinline__ int in_bn_channel(const Geo& gn, int c) {
 // one s/t-net BatchNorm running-stat update (the link's extra workgroups)
 __device__ __forceinline__ void net_running_block(const rnvp_coupling_args& a, int i, double* tmp) {
     const rnvp_bn_running r = a.net_running[i];
-    block_shard_sums(r.sums, r.C, r.shards, 0, r.C, tmp, tmp + r.C);
-    const float mom = a.momentum;
-    for (int c = threadIdx.x; c < r.C; c += blockDim.x) {
-        double mean = tmp[c] / r.count;
-        double var = tmp[r.C + c] / r.count - mean * mean;
-        if (var < 0) var = 0;
-        double unb = r.count > 1 ? var * r.count / (r.count - 1) : var;
-        r.rmean[c] = (1.f - mom) * r.rmean[c] + mom * (float)mean;
-        r.rvar[c] = (1.f - mom) * r.rvar[c] + mom * (float)unb;
-    }
-    if (threadIdx.x == 0 && r.nbt) r.nbt[0] += 1;
+    bn_running_site(r, a.momentum, tmp);
 }
 
 // ---------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 
 #include "coupling_common.h"
 
-extern "C" int rnvp_version(void) { return 108; }
+extern "C" int rnvp_version(void) { return 109; }
 
 extern "C" int rnvp_struct_size(int which) {
     switch (which) {
@@ -474,16 +474,7 @@ extern "C" int rnvp_flow_lp_finish(double* prior, float* ldj, float* logdet, int
 __global__ void k_bn_running(const rnvp_bn_running* __restrict__ d, float mom) {
     extern __shared__ double tmp[];   // [2*C]
     const rnvp_bn_running r = d[blockIdx.x];
-    block_shard_sums(r.sums, r.C, r.shards, 0, r.C, tmp, tmp + r.C);
-    for (int c = threadIdx.x; c < r.C; c += blockDim.x) {
-        double mean = tmp[c] / r.count;
-        double var = tmp[r.C + c] / r.count - mean * mean;
-        if (var < 0) var = 0;
-        double unb = r.count > 1 ? var * r.count / (r.count - 1) : var;
-        r.rmean[c] = (1.f - mom) * r.rmean[c] + mom * (float)mean;
-        r.rvar[c] = (1.f - mom) * r.rvar[c] + mom * (float)unb;
-    }
-    if (threadIdx.x == 0 && r.nbt) r.nbt[0] += 1;
+    bn_running_site(r, mom, tmp);
 }
 
 extern "C" int rnvp_bn_running_update(const rnvp_bn_running* d, int n, int max_c, float momentum, void* stream) {

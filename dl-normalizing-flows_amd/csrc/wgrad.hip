@@ -256,6 +256,7 @@ int wgrad_conv_status(const rnvp_wgrad_conv& v) {
     if ((v.cs_in & 7) || (v.cs_dy & 7) || v.cs_in < v.cin || v.cs_dy < v.n) return RNVP_E_INVALID;
     if (v.kp < v.ks * v.ks * v.cs_in) return RNVP_E_INVALID;
     if (!al16(v.x) || !al16(v.dy)) return RNVP_E_INVALID;
+    if (v.pro_bn_relu && v.pro.tab && (!v.pro.sums || !al16(v.pro.tab))) return RNVP_E_INVALID;
     return RNVP_OK;
 }
 
@@ -273,6 +274,15 @@ extern "C" int rnvp_wgrad_slabs(long long M) {
 }
 
 extern "C" int rnvp_wgrad_replicas(int nz) { return nz < 8 ? (nz < 1 ? 1 : nz) : 8; }
+
+// host only: the tap-shared kernel class (0 .. 3) conv c of the group runs in,
+// RNVP_E_UNSUPPORTED when the group takes the generic kernel
+extern "C" int rnvp_wgrad_class(const rnvp_wgrad_group* gin, int c) {
+    if (!gin || c < 0 || c >= gin->n_conv || gin->n_conv > RNVP_WGRAD_GROUP_MAX) return RNVP_E_INVALID;
+    rnvp_wgrad_group gt = *gin;
+    const int st = rnvp_wgrad_tap_prepare(&gt);
+    return st != RNVP_OK ? st : gt.conv[c].cls;
+}
 
 extern "C" int rnvp_conv2d_wgrad_grouped(const rnvp_wgrad_group* gin, void* stream) {
     if (!gin || gin->n_conv <= 0 || gin->n_conv > RNVP_WGRAD_GROUP_MAX) return RNVP_E_INVALID;

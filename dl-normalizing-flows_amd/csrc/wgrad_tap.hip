@@ -619,10 +619,8 @@ void wt_balance(rnvp_wgrad_group& sg, int cls, long long M, size_t lds) {
 
 }  // namespace
 
-// Launch of the tap-shared kernel for a bf16 group; RNVP_E_UNSUPPORTED when a
-// conv's shape is outside what it stages (the caller then uses the per-tap
-// kernel).  Fills task0 / tk (= ci tiles) / m_per_slab of the group's copy.
-int rnvp_wgrad_tap_launch(rnvp_wgrad_group* g, hipStream_t s) {
+// the checks of rnvp_wgrad_tap_launch and every conv's class / slab fields (host only)
+int rnvp_wgrad_tap_prepare(rnvp_wgrad_group* g) {
     if (g->dtype != RNVP_BF16) return RNVP_E_UNSUPPORTED;
     const long long M = (long long)g->B * g->H * g->W;
     const int H = g->H, W = g->W;
@@ -644,6 +642,19 @@ int rnvp_wgrad_tap_launch(rnvp_wgrad_group* g, hipStream_t s) {
         v.tk = (v.cs_in + wt_tci(cls) - 1) / wt_tci(cls);
         if (wt_tasks(v, cls) <= 0 || wt_tasks(v, cls) > (1ll << 28)) return RNVP_E_INVALID;
     }
+    return RNVP_OK;
+}
+
+// Launch of the tap-shared kernel for a bf16 group; RNVP_E_UNSUPPORTED when a
+// conv's shape is outside what it stages (the caller then uses the per-tap
+// kernel).  Fills task0 / tk (= ci tiles) / m_per_slab of the group's copy.
+int rnvp_wgrad_tap_launch(rnvp_wgrad_group* g, hipStream_t s) {
+    {
+        const int st = rnvp_wgrad_tap_prepare(g);
+        if (st != RNVP_OK) return st;
+    }
+    const long long M = (long long)g->B * g->H * g->W;
+    const int H = g->H, W = g->W;
     // ONE launch for the group -- the class kernel (its own register budget)
     // when every conv has the same class, else the all-class kernel (the
     // largest class's VGPRs for every task) -- or, from WT_SPLIT_MIN_M pixels

@@ -26,11 +26,18 @@ f64 = C.c_double
 
 class BNSrc(C.Structure):
     _fields_ = [("sums", vp), ("count", f64), ("mean", vp), ("var", vp), ("gamma", vp), ("beta", vp), ("eps", f32),
-                ("shards", i32)]
+                ("shards", i32), ("tab", vp)]
+
+
+def bn_tab_floats(c):
+    """Floats of one BatchNorm's finalized table (RNVP_BN_TAB_FLOATS): {mean,
+    rstd} in two flavours of the division by the count, per channel."""
+    return 4 * int(c)
 
 
 class BNRunning(C.Structure):
-    _fields_ = [("sums", vp), ("count", f64), ("C", i32), ("shards", i32), ("rmean", vp), ("rvar", vp), ("nbt", vp)]
+    _fields_ = [("sums", vp), ("count", f64), ("C", i32), ("shards", i32), ("rmean", vp), ("rvar", vp), ("nbt", vp),
+                ("eps", f32), ("tab", vp)]
 
 
 class ConvArgs(C.Structure):
@@ -165,9 +172,11 @@ _SIGS = {
     "rnvp_stat_shards": (i32, [i64]),
     "rnvp_conv2d": (i32, [C.POINTER(ConvArgs), vp]),
     "rnvp_conv2d_check": (i32, [C.POINTER(ConvArgs)]),
+    "rnvp_conv2d_family": (i32, [C.POINTER(ConvArgs)]),
     "rnvp_wgrad_slabs": (i32, [i64]),
     "rnvp_wgrad_replicas": (i32, [i32]),
     "rnvp_conv2d_wgrad_grouped": (i32, [C.POINTER(WgradGroup), vp]),
+    "rnvp_wgrad_class": (i32, [C.POINTER(WgradGroup), i32]),
     "rnvp_bn_bwd_apply": (i32, [C.POINTER(BNBwdArgs), vp]),
     "rnvp_weight_norm_fwd": (i32, [vp, i32, i32, i32, i32, vp]),
     "rnvp_weight_norm_tiles": (i32, [i32, i32, i32]),
@@ -218,7 +227,7 @@ class _Lib:
             fn.restype = res
             fn.argtypes = args
             raw = name in ("rnvp_version", "rnvp_struct_size", "rnvp_stat_shards", "rnvp_wgrad_slabs", "rnvp_wgrad_replicas",
-                           "rnvp_link_nclass", "rnvp_conv2d_check", "rnvp_grad_sumsq_parts",
+                           "rnvp_link_nclass", "rnvp_conv2d_check", "rnvp_conv2d_family", "rnvp_wgrad_class", "rnvp_grad_sumsq_parts",
                            "rnvp_weight_norm_tiles", "rnvp_weight_norm_opt_blocks",
                            "rnvp_net_group_prepare") or res is not i32
             setattr(self, name[len("rnvp_"):], fn if raw else self._wrap(name, fn))

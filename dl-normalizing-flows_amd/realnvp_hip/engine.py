@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import (BNBwdArgs, BNRunning, BNSrc, ConvArgs, CouplingArgs, NetStep, WgradConv, WgradGroup, WNDesc,
-                   NET_GROUP_MAX, RNVP_BF16, RNVP_F32, RNVP_STEP_BN_BWD, RNVP_STEP_CONV, WGRAD_GROUP_MAX)
+                   bn_tab_floats, NET_GROUP_MAX, RNVP_BF16, RNVP_F32, RNVP_STEP_BN_BWD, RNVP_STEP_CONV, WGRAD_GROUP_MAX)
 from .net import backward_program, build_program, chan_stride, round_up
 
 BN_EPS = 1e-5
@@ -38,6 +38,13 @@ NET_GROUP = True
 # operand staging where the library supports it (rnvp_conv_args.bp, deep
 # scales); False keeps every apply a launch of its own (tests compare the two)
 FOLD_BN = True
+# The s/t net's BatchNorms keep a finalized table (rnvp_bn_src.tab: mean, rstd
+# per channel) in the saved arena, written once per forward
+# by the running-statistics update and read by every backward consumer
+# (data-gradient epilogues, the folded / standalone BatchNorm backward)
+# instead of each workgroup re-deriving it from the sharded sums; False keeps
+# the shard reduction everywhere (A/B runs, tests)
+BN_TABLES = True
 
 
 def stream_ptr():
@@ -127,9 +134,9 @@ class Arena:
         return s, o + nb
 
 
-def _bn_src(sums, count, mean, var, gamma, beta, shards=1):
+def _bn_src(sums, count, mean, var, gamma, beta, shards=1, tab=None):
     return BNSrc(sums or None, float(count), mean or None, var or None, gamma or None, beta or None, BN_EPS,
-                 int(shards))
+                 int(shards), (tab or None) if sums else None)
 
 
 def stat_shards(M):
@@ -342,6 +349,12 @@ class CouplingEngine:
             if b != "h0":
                 ar.add(b, M * chan_stride(ch) * esz)
         ar.add("u", B * self.C * H * W * 4)
+        # the net BatchNorms' finalized tables: ahead of the sums, outside the
+        # range the end of a step (or the next forward) zeroes (BN_TABLES off
+        # when the arena is made: no tables, and the update writes none)
+        if training and BN_TABLES:
+            for bn, spec in self.P.bns.items():
+                ar.add("t:" + bn, 4 * bn_tab_floats(spec.c))
         ar.add("in_sums", COUPLING_SHARDS * 2 * self.Cb * 8)
         ar.add("out_sums", COUPLING_SHARDS * 2 * self.Cb * 8)
         # coupling links (rnvp_coupling_out_u / _link_fwd): u's sums per pixel class, the prior's sums
@@ -354,19 +367,26 @@ class CouplingEngine:
             ar.add("s:" + bn, sh * 2 * spec.c * 8)
         ar.alloc(device, zero=True)   # the sums start zero (persistent arenas keep them zero between steps)
         sv = dict(arena=ar, B=B, H=H, W=W, dtype=dtype, training=training, shards=sh)
-        # running-stat update table for the net BNs
         if training and self.P.bns:
-            T = self._tensors()
-            rows = []
-            for bn, spec in self.P.bns.items():
-                r = BNRunning(ar.ptr("s:" + bn), float(M), spec.c, sh, T[bn + "running_mean"].data_ptr(),
-                              T[bn + "running_var"].data_ptr(), T[bn + "num_batches_tracked"].data_ptr())
-                rows.append(r)
-            tab = (BNRunning * len(rows))(*rows)
-            sv["bn_table"] = upload(bytes(tab), device)
-            sv["bn_n"] = len(rows)
-            sv["bn_cmax"] = max(spec.c for spec in self.P.bns.values())
+            self._bn_running_table(sv)
         return sv
+
+    def _bn_running_table(self, sv):
+        """The net BatchNorms' running-statistics rows (rnvp_bn_running) of a
+        training arena; the update also writes each BatchNorm's finalized
+        table (mean, rstd: no parameter is read, so the rows do not follow the
+        parameters' storage)."""
+        ar, T = sv["arena"], self._tensors()
+        M, sh = sv["B"] * sv["H"] * sv["W"], sv["shards"]
+        rows = []
+        for bn, spec in self.P.bns.items():
+            rows.append(BNRunning(ar.ptr("s:" + bn), float(M), spec.c, sh, T[bn + "running_mean"].data_ptr(),
+                                  T[bn + "running_var"].data_ptr(), T[bn + "num_batches_tracked"].data_ptr(),
+                                  BN_EPS, ar.ptr("t:" + bn) if ar.has("t:" + bn) else None))
+        tab = (BNRunning * len(rows))(*rows)
+        sv["bn_table"] = upload(bytes(tab), ar.buf.device)
+        sv["bn_n"] = len(rows)
+        sv["bn_cmax"] = max(spec.c for spec in self.P.bns.values())
 
     def _pool_key(self, B, H, W, dtype, device, training):
         return (B, H, W, dtype, str(device), bool(training))
@@ -499,10 +519,12 @@ class CouplingEngine:
         a.cs_st = chan_stride(self.P.buf_ch["st"])
         return a
 
-    def _bn(self, T, bn, training, sums_ptr, M):
+    def _bn(self, T, bn, training, sums_ptr, M, tab=None):
+        """tab: the BatchNorm's finalized table (backward sources only: the
+        forward's prologues run before it is written)."""
         return _bn_src(sums_ptr if training else None, M, T[bn + "running_mean"].data_ptr(),
                        T[bn + "running_var"].data_ptr(), T[bn + "weight"].data_ptr(), T[bn + "bias"].data_ptr(),
-                       stat_shards(M))
+                       stat_shards(M), tab)
 
     def _net_forward(self, T, sv, ws, training, s):
         """The s/t net's conv launches.  Their argument structs depend only on
@@ -665,7 +687,7 @@ class CouplingEngine:
         # the net's data-gradient chain and grouped weight gradients: argument
         # structs cached per (saved arena, scratch, weight set); only the
         # BatchNorm-affine gradient pointers follow this call's grad block
-        key = (ws["key"], id(sc), bool(training), FOLD_BN)
+        key = (ws["key"], id(sc), bool(training), FOLD_BN, BN_TABLES)
         plan = sv.get("bwd_plan")
         if plan is None or plan[0] != key:
             plan = (key, self._bwd_args(T, sv, sc, ws, training))
@@ -760,6 +782,14 @@ class CouplingEngine:
         esz = DTYPES[dtype][1]
         ar, sar, war = sv["arena"], sc["arena"], ws["arena"]
         items, groups = [], []
+
+        def tab(bn):
+            # the forward's running-statistics update wrote it (training arenas only)
+            ok = BN_TABLES and training and "bn_table" in sv and ar.has("t:" + bn)
+            return ar.ptr("t:" + bn) if ok else None
+        # (the weight-gradient prologues keep the shard reduction: their table
+        # work was hidden behind the first stage's loads, no launch got shorter)
+
         ent = []        # [kind, args, bytes, flops, bn, reads, writes, BwdStep, tmp name]
         wg_bytes = wg_flops = 0.0
         wbase = sc["wg_ws"].data_ptr()
@@ -780,7 +810,7 @@ class CouplingEngine:
                 if op.pro_bn:
                     c.epi_relu_bn_bwd = 1
                     c.epi_x = ar.ptr(op.x)
-                    c.epi = self._bn(T, op.pro_bn, training, ar.ptr("s:" + op.pro_bn), M)
+                    c.epi = self._bn(T, op.pro_bn, training, ar.ptr("s:" + op.pro_bn), M, tab(op.pro_bn))
                     c.epi_sums = sar.ptr("e:" + op.pro_bn)
                 if sc["ws"] is not None:
                     c.ws, c.ws_elems = sc["ws"].data_ptr(), sc["ws_elems"]
@@ -798,7 +828,7 @@ class CouplingEngine:
                 c = BNBwdArgs()
                 c.dtype, c.M, c.C, c.cs = dt, M, spec.cin, cs_in
                 c.g, c.x = sar.ptr(st.tmp), ar.ptr(op.x)
-                c.bn = self._bn(T, bn, training, ar.ptr("s:" + bn), M)
+                c.bn = self._bn(T, bn, training, ar.ptr("s:" + bn), M, tab(bn))
                 c.sums = sar.ptr("e:" + bn)
                 c.sum_shards = sc["shards"]
                 c.dx = sar.ptr(st.gx)

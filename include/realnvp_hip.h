@@ -101,14 +101,38 @@ typedef struct rnvp_bn_src {
     const float* beta;    /* affine bias, NULL = 0 */
     float eps;
     int shards;           /* >= 1 */
+    /* optional finalized table of this BatchNorm (train mode: sums != NULL),
+     * written by the running-statistics update of the same forward pass
+     * (rnvp_bn_running.tab) -- fp32 [C][4], one 16-byte entry per channel,
+     * 16-byte aligned: {mean, rstd} with mean = sum * (1 / count) (what the
+     * register tables of the deep-scale and halo kernels form), then {mean,
+     * rstd} with mean = sum / count (every other kernel, the apply and the
+     * fold); rstd = 1/sqrt(var + eps), var = sum2 / count - mean^2 with the
+     * same flavour of division, clamped at 0.  Contract: every float is the
+     * fp32 rounding of that float64 expression of the shard sums added in
+     * shard order.  A reader loads the pair its own formula would give instead
+     * of reducing the shards, and forms scale = gamma * rstd and shift = beta -
+     * mean * gamma * rstd in fp32 exactly as it does after its own reduction:
+     * the table holds no scale / shift (their fp32 formula is not the
+     * rounding of a float64 value, and the backward's ReLU decisions must be
+     * the forward's).  NULL: the table is derived from sums (eval mode,
+     * forward prologues -- the table is not written yet -- and callers
+     * without one). */
+    const float* tab;
 } rnvp_bn_src;
+#define RNVP_BN_TAB_FLOATS(C) (4 * (C))
 int rnvp_stat_shards(long long M);
 
 /* running-stat update of nn.BatchNorm2d in train mode, for n BN sites at once.
  * rm = (1-mom) rm + mom mean; rv = (1-mom) rv + mom var*count/(count-1); nbt += 1 */
+/* tab (optional): the site's finalized table (rnvp_bn_src.tab layout,
+ * RNVP_BN_TAB_FLOATS(C) floats) is written by the same workgroup from the same
+ * sums with eps -- once per forward instead of once per workgroup of every
+ * backward consumer. */
 typedef struct rnvp_bn_running {
     const double* sums; double count; int C; int shards;
     float* rmean; float* rvar; long long* nbt;
+    float eps; float* tab;
 } rnvp_bn_running;
 int rnvp_bn_running_update(const rnvp_bn_running* descs_device, int n, int max_c, float momentum, void* stream);
 
@@ -176,6 +200,12 @@ int rnvp_conv2d(const rnvp_conv_args* a, void* stream);
  * dispatch's own support limits, nothing launched): the host uses it to
  * decide which BatchNorm-backward applies fold into their consumer (bp). */
 int rnvp_conv2d_check(const rnvp_conv_args* a);
+/* host only, nothing launched: the kernel family rnvp_conv2d(a) would run on
+ * (deep-scale tiles, the wide scales' streaming 1x1, their band 3x3, or one of
+ * the remaining families), or a negative RNVP_E_* code.  The tests use it to
+ * assert that a shape reaches the family it is meant to cover. */
+enum { RNVP_FAMILY_OTHER = 0, RNVP_FAMILY_DEEP = 1, RNVP_FAMILY_S1 = 2, RNVP_FAMILY_BAND = 3 };
+int rnvp_conv2d_family(const rnvp_conv_args* a);
 
 /* grouped weight gradient: the wgrads of every conv of one coupling's s/t
  * network in ONE launch (they are independent of each other once the
@@ -207,6 +237,11 @@ typedef struct rnvp_wgrad_group {
 int rnvp_wgrad_slabs(long long M);
 int rnvp_wgrad_replicas(int nz);
 int rnvp_conv2d_wgrad_grouped(const rnvp_wgrad_group* g, void* stream);
+/* host only, nothing launched: the tap-shared bf16 kernel class conv c of the
+ * group runs in (0: 3x3 wide tiles, 1: 1x1 128 x 128, 2: 3x3 up to 32
+ * channels, 3: 1x1 up to 64), RNVP_E_UNSUPPORTED when the group takes the
+ * generic kernel */
+int rnvp_wgrad_class(const rnvp_wgrad_group* g, int c);
 
 /* batch-norm backward apply (train mode), the second half of BN backward:
  * dx = gamma*rstd*(g - sum_g/M - xhat * sum_gxhat/M) (+ residual) (+= dx if accumulate)

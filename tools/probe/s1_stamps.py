@@ -24,7 +24,23 @@ lib.probe_s1.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 PH = ["prologue", "tiles", "stats"]
 
 
-def case(name, B, H, W, cin, cout, pro=False, stats=False, residual=False, acc=False, dgrad=False, bp=False):
+def _table(sums, M, C_, sh):
+    """The finalized table of a BatchNorm (rnvp_bn_src.tab) from its sums, written
+    by the product library's running-statistics update."""
+    from realnvp_hip import _lib
+    from realnvp_hip.engine import upload
+    dev = sums.device
+    tab = torch.zeros(_lib.bn_tab_floats(C_), device=dev)
+    rm, rv = torch.zeros(C_, device=dev), torch.ones(C_, device=dev)
+    row = _lib.BNRunning(sums.data_ptr(), float(M), C_, sh, rm.data_ptr(), rv.data_ptr(), None, 1e-5, tab.data_ptr())
+    d = upload(bytes((_lib.BNRunning * 1)(row)), dev)
+    _lib.lib().bn_running_update(d.data_ptr(), 1, C_, 0.1, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return tab
+
+
+def case(name, B, H, W, cin, cout, pro=False, stats=False, residual=False, acc=False, dgrad=False, bp=False,
+         tab=False):
     dev = "cuda"
     M = B * H * W
     csi, cso = chan_stride(cin), chan_stride(cout)
@@ -39,6 +55,8 @@ def case(name, B, H, W, cin, cout, pro=False, stats=False, residual=False, acc=F
     sums_out = torch.zeros(sh, 2, cout, device=dev, dtype=torch.float64)
     gam = torch.ones(max(cin, cout), device=dev)
     bet = torch.zeros(max(cin, cout), device=dev)
+    # tab: the backward BatchNorm sources (epi, bp_bn) carry their finalized table
+    tb = _table(sums_in, M, max(cin, cout), sh).data_ptr() if tab else None
     a = ConvArgs()
     a.dtype = 1
     a.B, a.H, a.W, a.ks = B, H, W, 1
@@ -55,14 +73,14 @@ def case(name, B, H, W, cin, cout, pro=False, stats=False, residual=False, acc=F
     if dgrad:
         a.epi_relu_bn_bwd = 1
         a.epi_x = r.data_ptr()
-        a.epi = BNSrc(sums_in.data_ptr(), float(M), None, None, gam.data_ptr(), bet.data_ptr(), 1e-5, sh)
+        a.epi = BNSrc(sums_in.data_ptr(), float(M), None, None, gam.data_ptr(), bet.data_ptr(), 1e-5, sh, tb)
         a.epi_sums = sums_out.data_ptr()
     if bp:   # BatchNorm-backward prologue: x is the pre-apply gradient, t the BatchNorm input
         t = torch.randn(M, csi, device=dev).to(torch.bfloat16)
         side = torch.zeros(M, csi, device=dev).to(torch.bfloat16)
         dgb = torch.zeros(2, cin, device=dev)
         a.bp, a.bp_x, a.bp_sums, a.bp_shards = 1, t.data_ptr(), sums_in.data_ptr(), sh
-        a.bp_bn = BNSrc(sums_in.data_ptr(), float(M), None, None, gam.data_ptr(), bet.data_ptr(), 1e-5, sh)
+        a.bp_bn = BNSrc(sums_in.data_ptr(), float(M), None, None, gam.data_ptr(), bet.data_ptr(), 1e-5, sh, tb)
         a.bp_out, a.bp_dgamma, a.bp_dbeta = side.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr()
     st = torch.zeros(8192 * 8, dtype=torch.int64, device=dev)
     s = torch.cuda.current_stream().cuda_stream
@@ -94,10 +112,14 @@ CASES = [
     ("s2 64->64 pro+res", 64, 32, 32, 64, 64, dict(pro=True, residual=True)),
     ("s2 64->64 dgrad", 64, 32, 32, 64, 64, dict(dgrad=True)),
     ("s2 64->64 dgrad+bp", 64, 32, 32, 64, 64, dict(dgrad=True, bp=True)),
+    ("s2 64->64 dgrad tab", 64, 32, 32, 64, 64, dict(dgrad=True, tab=True)),
+    ("s2 64->64 dgrad+bp tab", 64, 32, 32, 64, 64, dict(dgrad=True, bp=True, tab=True)),
     ("s2 64->64 plain", 64, 32, 32, 64, 64, dict()),
     ("s1 32->32 pro+stats", 64, 64, 64, 32, 32, dict(pro=True, stats=True)),
     ("s1 32->32 dgrad", 64, 64, 64, 32, 32, dict(dgrad=True)),
     ("s1 32->32 dgrad+bp", 64, 64, 64, 32, 32, dict(dgrad=True, bp=True)),
+    ("s1 32->32 dgrad tab", 64, 64, 64, 32, 32, dict(dgrad=True, tab=True)),
+    ("s1 32->32 dgrad+bp tab", 64, 64, 64, 32, 32, dict(dgrad=True, bp=True, tab=True)),
     ("s1 32->32 plain", 64, 64, 64, 32, 32, dict()),
 ]
 
