@@ -91,7 +91,8 @@ class StepCtl(C.Structure):
                 ("decay", i32), ("decay_rate", f64), ("decay_steps", i64),
                 ("max_norm", f32),
                 ("lr", f32), ("grad_scale", f32), ("grad_norm", f32), ("skip", i32),
-                ("n_clipped", i64), ("n_skipped", i64)]
+                ("n_clipped", i64), ("n_skipped", i64),
+                ("accum_steps", i32), ("micro", i32), ("hold", i32)]
 
 
 class AdamArgs(C.Structure):
@@ -206,6 +207,7 @@ _SIGS = {
     "rnvp_step_increment": (i32, [vp, vp]),
     "rnvp_grad_sumsq_parts": (i32, [i64]),
     "rnvp_grad_sumsq": (i32, [C.POINTER(AdamArgs), i64, vp, i32, vp]),
+    "rnvp_grad_accumulate": (i32, [C.POINTER(AdamArgs), vp, i64, vp, vp, i32, vp]),
     "rnvp_step_control": (i32, [vp, vp, vp, i32, vp]),
     "rnvp_adam_range": (i32, [C.POINTER(AdamArgs), i64, vp]),
     "rnvp_step_advance": (i32, [vp, vp, vp]),

@@ -5,7 +5,9 @@ Importable and usable without a GPU.
 A FlowTrainer built with ``lr_schedule`` and / or ``max_grad_norm`` keeps a
 device-resident ``rnvp_step_ctl`` block; ``rnvp_step_control`` evaluates the
 schedule there from the optimizer's step counter, so a captured step follows
-it without re-capture.
+it without re-capture.  With ``accum_steps = K > 1`` the same block counts
+the micro-steps of the open optimizer step (``micro``) and decides on the
+device which replay holds and which applies.
 """
 import math
 
@@ -92,11 +94,19 @@ def check_max_grad_norm(v):
     return v
 
 
-def fill_ctl(ctl, base_lr, schedule, max_grad_norm):
+def check_accum_steps(k):
+    """micro-steps per optimizer step: an int in 1 .. 65536 (1 = no accumulation)"""
+    if isinstance(k, bool) or not isinstance(k, int) or not (1 <= k <= 65536):
+        raise ValueError("accum_steps must be an int in 1 .. 65536, got %r" % (k,))
+    return k
+
+
+def fill_ctl(ctl, base_lr, schedule, max_grad_norm, accum_steps=1):
     """the configuration fields of a _lib.StepCtl"""
     sch = schedule if schedule is not None else StepSchedule()
     ctl.base_lr = base_lr
     ctl.warmup_start, ctl.warmup_steps = sch.warmup_start, sch.warmup_steps
     ctl.decay, ctl.decay_rate, ctl.decay_steps = DECAYS[sch.decay], sch.decay_rate, sch.decay_steps
     ctl.max_norm = max_grad_norm if max_grad_norm is not None else 0.0
+    ctl.accum_steps = check_accum_steps(accum_steps)
     return ctl

@@ -25,6 +25,13 @@ MI355X-specific structure:
     decided on the device every step (rnvp_step_control), from a block the
     host only writes with stream-ordered copies -- the captured graph follows
     a schedule, set_lr() or set_max_grad_norm() without re-capture.
+  * optional gradient accumulation (accum_steps=K): every step() is a
+    micro-step of the same captured graph; the block counts them, K - 1
+    steps add their gradient into an fp32 accumulator (rnvp_grad_accumulate)
+    and hold -- parameters, moments, weight images and the step counter keep
+    their bits -- and the K-th leaves the average in the gradient arena,
+    decides on it and applies.  The dequantisation noise then has a counter
+    of its own, which moves every micro-step.
 """
 import ctypes as C
 import gc
@@ -104,15 +111,22 @@ class FlowTrainer:
     def __init__(self, model, batch_size, lr=5e-4, weight_decay=5e-5, betas=(0.9, 0.999), eps=1e-8,
                  scale_reg=5e-5, dtype="bf16", seed=0, process_group=None, bucket_mb=25, overlap=False,
                  comm="overlap", reduce_dtype="fp32", param_pass=None, chain=True, max_grad_norm=None,
-                 lr_schedule=None):
-        from .stepctl import StepSchedule, check_max_grad_norm
+                 lr_schedule=None, accum_steps=1):
+        from .stepctl import StepSchedule, check_accum_steps, check_max_grad_norm
         if lr_schedule is not None and not isinstance(lr_schedule, StepSchedule):
             raise ValueError("lr_schedule must be a realnvp_hip.stepctl.StepSchedule or None")
         self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.lr_schedule = lr_schedule
+        self.accum_steps = check_accum_steps(accum_steps)
+        if self.accum_steps > 1 and process_group is not None:
+            raise ValueError("accum_steps > 1 with a process_group is not supported: every micro-step would "
+                             "all-reduce (deferring it to the last one is not built)")
         # gradient-norm clipping (and the non-finite skip) is part of the step's
-        # launch schedule: fixed at construction
-        self.clip = self.max_grad_norm is not None
+        # launch schedule: fixed at construction.  Gradient accumulation takes
+        # the same schedule (the gradients final in the arena before ONE
+        # parameter pass), with the accumulate pass where the norm is;
+        # max_grad_norm=None then means guard only
+        self.clip = self.max_grad_norm is not None or self.accum_steps > 1
         self.model = model
         self.dev = next(model.parameters()).device
         if self.dev.type != "cuda":
@@ -198,18 +212,25 @@ class FlowTrainer:
         stream-ordered fills (set_lr, set_max_grad_norm); nothing of it is a
         captured launch argument but its address."""
         self.ctl_buf = self.gs_partials = None
+        # accumulation: the fp32 accumulator of the gradient arena, and the
+        # dequantisation noise's own counter (the step counter stands still on
+        # a held micro-step; this one moves every micro-step, skipped or not)
+        self.acc = self.noise_t = None
         if self.lr_schedule is None and not self.clip:
             return
         from ._lib import StepCtl
         from .engine import upload
         from .stepctl import StepSchedule, fill_ctl
-        c = fill_ctl(StepCtl(), self.lr, self.lr_schedule, self.max_grad_norm)
+        c = fill_ctl(StepCtl(), self.lr, self.lr_schedule, self.max_grad_norm, self.accum_steps)
         c.lr = self.lr * (self.lr_schedule or StepSchedule()).factor(0)
         c.grad_scale = 1.0
         self.ctl_buf = upload(bytes(c), self.dev)
         if self.clip:
             self.gs_parts = int(_lib.lib().grad_sumsq_parts(self.n))
             self.gs_partials = torch.zeros(self.gs_parts, device=self.dev, dtype=torch.float64)
+        if self.accum_steps > 1:
+            self.acc = torch.zeros(self.n, device=self.dev, dtype=torch.float32)
+            self.noise_t = torch.zeros(1, device=self.dev, dtype=torch.int64)
 
     def _ctl_field(self, name):
         """a one-element tensor view of a field of the control block"""
@@ -241,25 +262,30 @@ class FlowTrainer:
     def set_max_grad_norm(self, v):
         """The clipping threshold from the next step on (None: no clipping, the
         non-finite skip stays); a stream-ordered write, no re-capture.  Needs a
-        trainer built with max_grad_norm: the norm pass is part of its step."""
+        trainer built with max_grad_norm (or accum_steps > 1, which takes the
+        same schedule): the norm pass is part of its step."""
         from .stepctl import check_max_grad_norm
         if not self.clip:
-            raise RuntimeError("set_max_grad_norm needs a FlowTrainer built with max_grad_norm (the gradient-norm "
-                               "pass is part of the step's launch schedule)")
+            raise RuntimeError("set_max_grad_norm needs a FlowTrainer built with max_grad_norm or accum_steps > 1 "
+                               "(the gradient-norm pass is part of the step's launch schedule)")
         self.max_grad_norm = check_max_grad_norm(v)
         self._ctl_field("max_norm").fill_(self.max_grad_norm if self.max_grad_norm is not None else 0.0)
 
     def step_control_state(self):
         """What rnvp_step_control decided in the last step: lr, grad_norm (the
         pre-clip norm), grad_scale, skip, and the counters n_clipped /
-        n_skipped.  Synchronises (a device-to-host copy): the one documented
-        sync of the step control."""
+        n_skipped; hold (the last step was a held micro-step of an
+        accumulating trainer: skip is then set too, grad_norm and the counters
+        are the last optimizer step's) and micro (micro-steps accumulated in
+        the open optimizer step).  Synchronises (a device-to-host copy): the
+        one documented sync of the step control."""
         if self.ctl_buf is None:
             raise RuntimeError("this FlowTrainer has no step control (built without lr_schedule / max_grad_norm)")
         from ._lib import StepCtl
         c = StepCtl.from_buffer_copy(bytes(self.ctl_buf.cpu().numpy()))
         return {"lr": c.lr, "grad_norm": c.grad_norm, "grad_scale": c.grad_scale, "skip": int(c.skip),
-                "n_clipped": int(c.n_clipped), "n_skipped": int(c.n_skipped)}
+                "n_clipped": int(c.n_clipped), "n_skipped": int(c.n_skipped), "hold": int(c.hold),
+                "micro": int(c.micro)}
 
     def _open_step(self):
         """first launch of a step with a control block: this step's learning
@@ -270,13 +296,20 @@ class FlowTrainer:
 
     def _grad_norm_control(self):
         """Between the last gradient (after the all-reduce) and the first Adam
-        launch: the arena's sum of squares, then the clip scale / skip."""
+        launch: the arena's sum of squares, then the clip scale / skip.
+        Accumulating: the accumulate pass in the norm's place (it leaves the
+        averaged gradient and its partials on the final micro-step), then the
+        control's hold / apply decision."""
         if not self.clip:
             return
         L = _lib.lib()
         s = stream_ptr()
-        _launch("param", 5 * self.n, 0.0, L.grad_sumsq, C.byref(self._opt_all), self.n, self.gs_partials.data_ptr(),
-                self.gs_parts, s)
+        if self.acc is not None:
+            _launch("param", 12 * self.n, 0.0, L.grad_accumulate, C.byref(self._opt_all), self.acc.data_ptr(), self.n,
+                    self.ctl_buf.data_ptr(), self.gs_partials.data_ptr(), self.gs_parts, s)
+        else:
+            _launch("param", 5 * self.n, 0.0, L.grad_sumsq, C.byref(self._opt_all), self.n,
+                    self.gs_partials.data_ptr(), self.gs_parts, s)
         _launch("param", 8 * self.gs_parts + 64, 0.0, L.step_control, self.ctl_buf.data_ptr(),
                 self.step_t.data_ptr(), self.gs_partials.data_ptr(), self.gs_parts, s)
 
@@ -285,6 +318,13 @@ class FlowTrainer:
             _lib.lib().step_advance(self.step_t.data_ptr(), self.ctl_buf.data_ptr(), stream_ptr())
         else:
             _lib.lib().step_increment(self.step_t.data_ptr(), stream_ptr())
+        if self.noise_t is not None:
+            _lib.lib().step_increment(self.noise_t.data_ptr(), stream_ptr())
+
+    def _noise_counter(self):
+        """the Philox counter of the dequantisation noise: the step counter,
+        or the micro-step counter of an accumulating trainer"""
+        return (self.noise_t if self.noise_t is not None else self.step_t).data_ptr()
 
     # ------------------------------------------------------------------- plan
     def _build_plan(self, chain=True):
@@ -666,7 +706,7 @@ class FlowTrainer:
         B = self.B
         n = self.pix[0].numel()
         if not self.external_input:
-            L.logit_fwd(self.pix.data_ptr(), None, self.seed, 0, self.step_t.data_ptr(), 0.9, self.xl.data_ptr(),
+            L.logit_fwd(self.pix.data_ptr(), None, self.seed, 0, self._noise_counter(), 0.9, self.xl.data_ptr(),
                         self.logdet.data_ptr(), B, n, s)
         self.ldj.zero_()
         late_ready = self._wn_prepare()
@@ -709,7 +749,7 @@ class FlowTrainer:
         n_el, esz = x0.numel(), 2 if self.dtype == "bf16" else 4
         cs_h0 = a0.cs_h0
         if not self.external_input:
-            _launch("logit", 8 * n_el, 0.0, L.flow_in_fwd, self.pix.data_ptr(), self.seed, self.step_t.data_ptr(),
+            _launch("logit", 8 * n_el, 0.0, L.flow_in_fwd, self.pix.data_ptr(), self.seed, self._noise_counter(),
                     0.9, self.xl.data_ptr(), self.logdet.data_ptr(), C.byref(a0), B, *x0.shape[1:], s)
             _launch("coupling", 4 * n_el + esz * x0[:, 0].numel() * cs_h0, 0.0, L.coupling_in_apply, C.byref(a0), s)
         else:
@@ -910,14 +950,18 @@ class FlowTrainer:
     def _snapshot(self):
         bufs = {n: b.detach().clone() for n, b in self.model.named_buffers()}
         ctl = self.ctl_buf.clone() if self.ctl_buf is not None else None
+        accum = (self.acc.clone(), self.noise_t.clone()) if self.acc is not None else None
         return (self.param.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.step_t.clone(),
-                self.ll_acc.clone(), bufs, ctl)
+                self.ll_acc.clone(), bufs, ctl, accum)
 
     def _restore(self, snap):
-        p, m, v, t, ll, bufs, ctl = snap
+        p, m, v, t, ll, bufs, ctl, accum = snap
         with torch.no_grad():
             if ctl is not None:
-                self.ctl_buf.copy_(ctl)     # the warm-up steps' counters
+                self.ctl_buf.copy_(ctl)     # the warm-up steps' counters (and micro)
+            if accum is not None:
+                self.acc.copy_(accum[0])
+                self.noise_t.copy_(accum[1])
             self.param.copy_(p)
             self.exp_avg.copy_(m)
             self.exp_avg_sq.copy_(v)
@@ -1119,8 +1163,13 @@ class FlowTrainer:
         from Philox(seed, counter = t), so (seed, t) is the whole RNG state
         (the reference saves none, train.py:249-250).  The
         saving rank is recorded: data-parallel ranks draw from seeds of their
-        own."""
-        return {"seed": int(self.seed), "rank": int(self.rank), "step": int(self.step_t.item())}
+        own.  An accumulating trainer draws micro-step j's noise from counter
+        j, a counter of its own ('noise_step'): the step counter stands still
+        while gradients accumulate."""
+        st = {"seed": int(self.seed), "rank": int(self.rank), "step": int(self.step_t.item())}
+        if self.noise_t is not None:
+            st["noise_step"] = int(self.noise_t.item())
+        return st
 
     def state_dict(self):
         """{'model': model.state_dict(), 'optimizer': torch-Adam-format state,
@@ -1128,14 +1177,20 @@ class FlowTrainer:
         noise stream so a resumed run draws the same noise as an unbroken one).
         A trainer with a step control adds 'step_control': the schedule's
         configuration, max_grad_norm and the two counters (the base rate
-        stays in the optimizer's param_groups[0]['lr'])."""
+        stays in the optimizer's param_groups[0]['lr']), accum_steps and
+        micro, and -- taken between the micro-steps of one optimizer step,
+        micro > 0 -- the gradient accumulator, so that the resumed run
+        completes that step bit for bit."""
         sd = {"model": self.model.state_dict(), "optimizer": self.optimizer_state_dict(),
               "rng": self.rng_state()}
         if self.ctl_buf is not None:
             st = self.step_control_state()
             sd["step_control"] = {"schedule": self.lr_schedule.config() if self.lr_schedule is not None else None,
                                   "max_grad_norm": self.max_grad_norm, "n_clipped": st["n_clipped"],
-                                  "n_skipped": st["n_skipped"]}
+                                  "n_skipped": st["n_skipped"], "accum_steps": self.accum_steps,
+                                  "micro": st["micro"]}
+            if st["micro"] > 0:
+                sd["step_control"]["accum"] = self.acc.clone()
         return sd
 
     def _load_step_control(self, sc):
@@ -1154,13 +1209,29 @@ class FlowTrainer:
         self._write_ctl_config()
         self._ctl_field("n_clipped").fill_(int(sc["n_clipped"]))
         self._ctl_field("n_skipped").fill_(int(sc["n_skipped"]))
+        if self.acc is not None:
+            micro = int(sc.get("micro", 0))
+            if not (0 <= micro < self.accum_steps) or (micro > 0) != ("accum" in sc):
+                raise ValueError("the checkpoint's accumulation state is inconsistent (micro=%d)" % micro)
+            self._ctl_field("micro").fill_(micro)
+            if micro > 0:
+                self.acc.copy_(sc["accum"].reshape(-1))
+            else:
+                self.acc.zero_()
 
     def load_state_dict(self, sd):
+        # the accumulator's scale and the meaning of micro are accum_steps':
+        # refused before anything is loaded
+        sc = sd.get("step_control")
+        k = int(sc.get("accum_steps", 1)) if sc is not None else 1
+        if k != self.accum_steps:
+            raise ValueError("the checkpoint was taken with accum_steps=%d, this FlowTrainer was built with "
+                             "accum_steps=%d" % (k, self.accum_steps))
         with torch.no_grad():
             self.model.load_state_dict(sd["model"])
         self.load_optimizer_state_dict(sd["optimizer"])
-        if sd.get("step_control") is not None:
-            self._load_step_control(sd["step_control"])
+        if sc is not None:
+            self._load_step_control(sc)
         rng = sd.get("rng")
         if rng is not None:
             # a checkpoint of THIS rank resumes its noise stream exactly; one
@@ -1171,6 +1242,8 @@ class FlowTrainer:
                 self.seed = int(rng["seed"])
                 self.drop_graph()    # the seed is a captured launch argument
             self.step_t.fill_(int(rng["step"]))
+            if self.noise_t is not None:
+                self.noise_t.fill_(int(rng.get("noise_step", 0)))
 
     def reset_optimizer(self):
         self.exp_avg.zero_()

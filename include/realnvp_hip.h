@@ -329,6 +329,11 @@ typedef struct rnvp_step_ctl {
     /* written by rnvp_step_control every step */
     float lr, grad_scale, grad_norm; int skip;
     long long n_clipped, n_skipped;
+    /* gradient accumulation ("step control" below); a block with accum_steps
+     * <= 1 (a zero-filled one included) behaves as one without these fields */
+    int accum_steps;                      /* configuration: micro-steps per optimizer step */
+    int micro;                            /* device: micro-steps already accumulated in the open optimizer step */
+    int hold;                             /* device: set on a held micro-step */
 } rnvp_step_ctl;
 /* ctl (optional, device): NULL = lr below, gradients as they are.  Non-NULL:
  * the Adam kernels (rnvp_weight_norm_bwd_adam, rnvp_adam_gather,
@@ -581,9 +586,29 @@ int rnvp_step_increment(long long* step, void* stream);
  * counters.  n_parts <= 2048.
  * rnvp_adam_range: rnvp_adam_update over [ad->param, ad->param + n) with the
  * arguments of ad, honouring ad->ctl.
- * rnvp_step_advance: rnvp_step_increment unless ctl->skip. */
+ * rnvp_step_advance: rnvp_step_increment unless ctl->skip.
+ *
+ * Gradient accumulation (ctl->accum_steps = K > 1): K launches of the same
+ * step make one optimizer step, and the device decides which of them applies.
+ * rnvp_grad_accumulate takes rnvp_grad_sumsq's place: one pass over the arena
+ * (rnvp_grad_sumsq's grid, granules and alignment rules; acc is an n-element
+ * fp32 accumulator, 16-byte aligned, zero before the first micro-step) that
+ *   while ctl->micro < K - 1 (a held micro-step) stores acc += grad and
+ *     writes neither grad nor the partials;
+ *   otherwise (the final micro-step) stores grad = (acc + grad) / (float)K
+ *     -- a correctly rounded fp32 division -- and acc = 0, and writes the
+ *     partials of the new grad, bitwise what rnvp_grad_sumsq writes for it.
+ * rnvp_step_control with partials then, while micro < K - 1, sets skip = 1 and
+ * hold = 1 and micro += 1 without reading the partials or touching grad_norm
+ * and the counters -- the Adam kernels and rnvp_step_advance leave everything
+ * as it is, as for any skipped step; otherwise it sets micro = 0, hold = 0 and
+ * decides as above from the accumulated gradient's partials (a non-finite
+ * value from any micro-step skips the whole optimizer step, counted once).
+ * The opening call (partials == NULL) leaves micro and hold alone. */
 int rnvp_grad_sumsq_parts(long long n);
 int rnvp_grad_sumsq(const rnvp_adam_args* ad, long long n, double* partials, int n_parts, void* stream);
+int rnvp_grad_accumulate(const rnvp_adam_args* ad, float* acc, long long n, const rnvp_step_ctl* ctl,
+                         double* partials, int n_parts, void* stream);
 int rnvp_step_control(rnvp_step_ctl* ctl, const long long* step, const double* partials, int n_parts, void* stream);
 int rnvp_adam_range(const rnvp_adam_args* ad, long long n, void* stream);
 int rnvp_step_advance(long long* step, const rnvp_step_ctl* ctl, void* stream);
