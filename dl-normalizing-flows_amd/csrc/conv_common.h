@@ -473,6 +473,12 @@ int rnvp_deep_auto_cfg(const rnvp_conv_args* a);
 // conv of the group is outside its staging limits (the caller falls back)
 int rnvp_wgrad_tap_launch(rnvp_wgrad_group* g, hipStream_t s);
 int rnvp_wgrad_tap_prepare(rnvp_wgrad_group* g);   // its checks and the convs' class fields, nothing launched
+// the model-wide launch of one tile class over many groups (rnvp_wgrad_multi,
+// realnvp_hip.h): the host-only planner (groups already argument-checked) and
+// the launch of an uploaded plan
+int rnvp_wgrad_tap_multi_plan(const rnvp_wgrad_group* groups, int n_groups, int cls, rnvp_wgrad_multi_conv* convs,
+                              int conv_cap, int* xcd_start, int* tasks, int task_cap, rnvp_wgrad_multi* m);
+int rnvp_wgrad_tap_multi_launch(const rnvp_wgrad_multi* m, hipStream_t s);
 
 // register-pipelined streaming 1x1 conv (conv_s1.hip): RNVP_E_UNSUPPORTED
 // outside bf16 / 1x1 / <= 64 channels / M >= 16k; dry: checks only

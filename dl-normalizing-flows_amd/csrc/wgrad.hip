@@ -328,3 +328,32 @@ extern "C" int rnvp_conv2d_wgrad_grouped(const rnvp_wgrad_group* gin, void* stre
     RNVP_LAUNCH_CHECK();
     return RNVP_OK;
 }
+
+extern "C" int rnvp_wgrad_multi_struct_size(int which) {
+    if (which == 0) return (int)sizeof(rnvp_wgrad_multi_conv);
+    if (which == 1) return (int)sizeof(rnvp_wgrad_multi);
+    return -1;
+}
+
+// host only: the plan of the model-wide tap-shared launch of class cls
+extern "C" int rnvp_wgrad_multi_plan(const rnvp_wgrad_group* groups, int n_groups, int cls,
+                                     rnvp_wgrad_multi_conv* convs, int conv_cap, int* xcd_start, int* tasks,
+                                     int task_cap, rnvp_wgrad_multi* m) {
+    if (!groups || n_groups <= 0 || !m || cls < 0 || cls > 3 || conv_cap < 0 || task_cap < 0) return RNVP_E_INVALID;
+    for (int g = 0; g < n_groups; ++g) {
+        const rnvp_wgrad_group& gr = groups[g];
+        if (gr.n_conv <= 0 || gr.n_conv > RNVP_WGRAD_GROUP_MAX) return RNVP_E_INVALID;
+        if (gr.dtype != RNVP_F32 && gr.dtype != RNVP_BF16) return RNVP_E_INVALID;
+        if (gr.B <= 0 || gr.H <= 0 || gr.W <= 0) return RNVP_E_INVALID;
+        for (int c = 0; c < gr.n_conv; ++c) {
+            const int st = wgrad_conv_status(gr.conv[c]);
+            if (st != RNVP_OK) return st;
+        }
+    }
+    return rnvp_wgrad_tap_multi_plan(groups, n_groups, cls, convs, conv_cap, xcd_start, tasks, task_cap, m);
+}
+
+extern "C" int rnvp_conv2d_wgrad_multi(const rnvp_wgrad_multi* m, void* stream) {
+    if (!m) return RNVP_E_INVALID;
+    return rnvp_wgrad_tap_multi_launch(m, (hipStream_t)stream);
+}

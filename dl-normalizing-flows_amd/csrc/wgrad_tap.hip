@@ -25,7 +25,9 @@
 #include "common.h"
 #include "conv_common.h"
 
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 namespace {
 
@@ -535,6 +537,40 @@ __global__ __launch_bounds__(WT_NT) void k_wgrad_tap(rnvp_wgrad_group g) {
     }
 }
 
+// The model-wide launch of one class (rnvp_wgrad_multi): the convs of many
+// groups, each with its own shape, in a device table; the block -> task map
+// is the uploaded plan (rnvp_wgrad_tap_multi_plan).  Block b serves XCD b % 8
+// and takes entry b / 8 of that XCD's task list: two dependent (uniform)
+// loads instead of the search over the by-value group.  Surplus blocks (the
+// grid is 8 x the longest list) leave before touching LDS.
+template <int CLS, bool KO>
+__global__ __launch_bounds__(WT_NT) void k_wgrad_multi(const rnvp_wgrad_multi_conv* __restrict__ convs,
+                                                       const int* __restrict__ xcd_start,
+                                                       const int2* __restrict__ tasks) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int xcd = blockIdx.x & 7, i = blockIdx.x >> 3;
+    const int t0 = xcd_start[xcd];
+    if (i >= xcd_start[xcd + 1] - t0) return;
+    const int2 tk = tasks[t0 + i];
+    const rnvp_wgrad_multi_conv& gc = convs[tk.x];
+    const WtConv cv{gc.x, gc.dy, gc.ws, gc.wsb, gc.pro, gc.cs_in, gc.cin, gc.cs_dy, gc.n, gc.kp, gc.pro_bn_relu,
+                    gc.nz, gc.nrep, gc.B, gc.H, gc.W, gc.m_per_slab};
+    const int tci = gc.tci, per = gc.tco * tci;
+    const int z = tk.y / per, rr = tk.y - z * per;
+    const int cot = rr / tci, cit = rr - cot * tci;
+    wt_body<CLS, KO>(cv, cot, cit, z, lds);
+}
+
+using WtMultiKernel = void (*)(const rnvp_wgrad_multi_conv*, const int*, const int2*);
+WtMultiKernel wt_multi_kernel(int cls, bool ko) {
+    switch (cls) {
+        case 0: return ko ? k_wgrad_multi<0, true> : k_wgrad_multi<0, false>;
+        case 1: return ko ? k_wgrad_multi<1, true> : k_wgrad_multi<1, false>;
+        case 2: return ko ? k_wgrad_multi<2, true> : k_wgrad_multi<2, false>;
+        default: return ko ? k_wgrad_multi<3, true> : k_wgrad_multi<3, false>;
+    }
+}
+
 using WtKernel = void (*)(rnvp_wgrad_group);
 WtKernel wt_kernel(int cls, bool ko) {
     switch (cls) {
@@ -698,6 +734,124 @@ int rnvp_wgrad_tap_launch(rnvp_wgrad_group* g, hipStream_t s) {
     }
     if (tasks > (1ll << 30)) return RNVP_E_INVALID;
     hipLaunchKernelGGL(wt_kernel(one_class ? g->conv[0].cls : -1, ko), dim3((unsigned)tasks), dim3(WT_NT), shm, s, *g);
+    RNVP_LAUNCH_CHECK();
+    return RNVP_OK;
+}
+
+// Host-only plan of the model-wide launch of class cls (realnvp_hip.h,
+// rnvp_wgrad_multi).  Every group is prepared as its own launch would prepare
+// it (class, slabs), so a task computes exactly what that launch's task does;
+// a group whose own launch would take another path (the per-class launches
+// from WT_SPLIT_MIN_M pixels, atomics, another k order) is refused.
+int rnvp_wgrad_tap_multi_plan(const rnvp_wgrad_group* groups, int n_groups, int cls, rnvp_wgrad_multi_conv* convs,
+                              int conv_cap, int* xcd_start, int* tasks, int task_cap, rnvp_wgrad_multi* m) {
+    struct Run { int conv, slab, tiles, tcost; long long cost; };
+    std::vector<rnvp_wgrad_multi_conv> cv;
+    std::vector<Run> runs;
+    std::vector<char> gko((size_t)n_groups, 1);
+    bool ko = true;
+    // pass 1: every group's own preparation and k order
+    std::vector<rnvp_wgrad_group> prep(groups, groups + n_groups);
+    for (int g = 0; g < n_groups; ++g) {
+        rnvp_wgrad_group& gt = prep[g];
+        const int st = rnvp_wgrad_tap_prepare(&gt);
+        if (st != RNVP_OK) return st;
+        if ((long long)gt.B * gt.H * gt.W >= WT_SPLIT_MIN_M) return RNVP_E_UNSUPPORTED;
+        for (int c = 0; c < gt.n_conv; ++c) {
+            if (gt.conv[c].nrep != gt.conv[c].nz) return RNVP_E_UNSUPPORTED;      // plain stores only
+            gko[g] = gko[g] && wt_lds_bytes(gt.conv[c].cls, gt.H, gt.W, true) <= 160 * 1024;
+        }
+        ko = ko && gko[g];
+    }
+    for (int g = 0; g < n_groups; ++g)
+        if ((bool)gko[g] != ko) return RNVP_E_UNSUPPORTED;
+    // pass 2: the class's convs and their (conv, slab) runs
+    size_t lds = 0;
+    long long n_task = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const rnvp_wgrad_group& gt = prep[g];
+        const long long M = (long long)gt.B * gt.H * gt.W;
+        for (int c = 0; c < gt.n_conv; ++c) {
+            const rnvp_wgrad_conv& v = gt.conv[c];
+            if (v.cls != cls) continue;
+            rnvp_wgrad_multi_conv e{};
+            e.x = v.x; e.dy = v.dy; e.ws = v.ws; e.wsb = v.wsb; e.pro = v.pro;
+            e.cs_in = v.cs_in; e.cin = v.cin; e.cs_dy = v.cs_dy; e.n = v.n; e.kp = v.kp;
+            e.pro_bn_relu = v.pro_bn_relu; e.nz = v.nz; e.nrep = v.nrep;
+            e.B = gt.B; e.H = gt.H; e.W = gt.W; e.cls = cls;
+            e.tco = (v.n + wt_tco(cls) - 1) / wt_tco(cls);
+            e.tci = v.tk;
+            e.m_per_slab = v.m_per_slab;
+            const size_t l = wt_lds_bytes(cls, gt.H, gt.W, ko);
+            lds = l > lds ? l : lds;
+            for (int z = 0; z < v.nz; ++z) {
+                const long long mb = (long long)z * v.m_per_slab;
+                const long long me = mb + v.m_per_slab < M ? mb + v.m_per_slab : M;
+                const int stages = (int)((me - mb + WT_SP - 1) / WT_SP);
+                Run r{(int)cv.size(), z, e.tco * e.tci, stages + WT_WG_OVERHEAD, 0};
+                r.cost = (long long)r.tiles * r.tcost;
+                runs.push_back(r);
+                n_task += r.tiles;
+            }
+            cv.push_back(e);
+        }
+    }
+    if (n_task > (1ll << 27)) return RNVP_E_INVALID;
+    *m = rnvp_wgrad_multi{};
+    m->cls = cls;
+    m->ko = ko ? 1 : 0;
+    m->n_conv = (int)cv.size();
+    m->n_task = (int)n_task;
+    m->lds_bytes = (int)lds;
+    // greedy, longest run first onto the least loaded XCD (ties: the lower
+    // index, so the plan is a function of its inputs alone)
+    std::vector<int> order(runs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return runs[a].cost > runs[b].cost; });
+    std::vector<int> list[8];
+    long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int len[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i : order) {
+        int x = 0;
+        for (int k = 1; k < 8; ++k)
+            if (load[k] < load[x]) x = k;
+        list[x].push_back(i);
+        load[x] += runs[i].cost;
+        len[x] += runs[i].tiles;
+    }
+    int longest = 0;
+    for (int x = 0; x < 8; ++x) {
+        m->xcd_cost[x] = load[x];
+        longest = len[x] > longest ? len[x] : longest;
+    }
+    m->grid = 8 * longest;
+    if (!convs) return RNVP_OK;                                        // counts only
+    if (!xcd_start || !tasks || m->n_conv > conv_cap || m->n_task > task_cap) return RNVP_E_INVALID;
+    for (size_t i = 0; i < cv.size(); ++i) convs[i] = cv[i];
+    int t = 0;
+    for (int x = 0; x < 8; ++x) {
+        // the heaviest tiles first: the XCD's tail is made of its lightest
+        std::stable_sort(list[x].begin(), list[x].end(), [&](int a, int b) { return runs[a].tcost > runs[b].tcost; });
+        xcd_start[x] = t;
+        for (int i : list[x]) {
+            const Run& r = runs[i];
+            for (int k = 0; k < r.tiles; ++k, ++t) {
+                tasks[2 * t] = r.conv;
+                tasks[2 * t + 1] = r.slab * r.tiles + k;
+            }
+        }
+    }
+    xcd_start[8] = t;
+    return RNVP_OK;
+}
+
+int rnvp_wgrad_tap_multi_launch(const rnvp_wgrad_multi* m, hipStream_t s) {
+    if (m->cls < 0 || m->cls > 3 || m->n_conv <= 0 || m->n_task <= 0) return RNVP_E_INVALID;
+    if (m->grid <= 0 || m->grid % 8 || (long long)m->grid < m->n_task || m->grid > (1 << 30)) return RNVP_E_INVALID;
+    if (m->lds_bytes <= 0 || m->lds_bytes > 160 * 1024) return RNVP_E_INVALID;
+    if (!m->convs || !m->xcd_start || !m->tasks) return RNVP_E_INVALID;
+    hipLaunchKernelGGL(wt_multi_kernel(m->cls, m->ko != 0), dim3((unsigned)m->grid), dim3(WT_NT), (size_t)m->lds_bytes, s,
+                       m->convs, m->xcd_start, (const int2*)m->tasks);
     RNVP_LAUNCH_CHECK();
     return RNVP_OK;
 }

@@ -117,6 +117,18 @@ class WgradGroup(C.Structure):
                 ("conv", WgradConv * WGRAD_GROUP_MAX)]
 
 
+class WgradMultiConv(C.Structure):
+    _fields_ = [("x", vp), ("dy", vp), ("ws", vp), ("wsb", vp), ("pro", BNSrc),
+                ("cs_in", i32), ("cin", i32), ("cs_dy", i32), ("n", i32), ("kp", i32), ("pro_bn_relu", i32),
+                ("nz", i32), ("nrep", i32), ("B", i32), ("H", i32), ("W", i32), ("cls", i32),
+                ("tco", i32), ("tci", i32), ("m_per_slab", i64)]
+
+
+class WgradMulti(C.Structure):
+    _fields_ = [("cls", i32), ("ko", i32), ("n_conv", i32), ("n_task", i32), ("grid", i32), ("lds_bytes", i32),
+                ("xcd_cost", i64 * 8), ("convs", vp), ("xcd_start", vp), ("tasks", vp)]
+
+
 class CouplingArgs(C.Structure):
     _fields_ = [("kind", i32), ("B", i32), ("C", i32), ("H", i32), ("W", i32), ("mask_config", i32),
                 ("coupling_bn", i32), ("training", i32), ("dtype", i32),
@@ -178,6 +190,10 @@ _SIGS = {
     "rnvp_wgrad_replicas": (i32, [i32]),
     "rnvp_conv2d_wgrad_grouped": (i32, [C.POINTER(WgradGroup), vp]),
     "rnvp_wgrad_class": (i32, [C.POINTER(WgradGroup), i32]),
+    "rnvp_wgrad_multi_plan": (i32, [C.POINTER(WgradGroup), i32, i32, C.POINTER(WgradMultiConv), i32, C.POINTER(i32),
+                                    C.POINTER(i32), i32, C.POINTER(WgradMulti)]),
+    "rnvp_conv2d_wgrad_multi": (i32, [C.POINTER(WgradMulti), vp]),
+    "rnvp_wgrad_multi_struct_size": (i32, [i32]),
     "rnvp_bn_bwd_apply": (i32, [C.POINTER(BNBwdArgs), vp]),
     "rnvp_weight_norm_fwd": (i32, [vp, i32, i32, i32, i32, vp]),
     "rnvp_weight_norm_tiles": (i32, [i32, i32, i32]),
@@ -229,7 +245,8 @@ class _Lib:
             fn.restype = res
             fn.argtypes = args
             raw = name in ("rnvp_version", "rnvp_struct_size", "rnvp_stat_shards", "rnvp_wgrad_slabs", "rnvp_wgrad_replicas",
-                           "rnvp_link_nclass", "rnvp_conv2d_check", "rnvp_conv2d_family", "rnvp_wgrad_class", "rnvp_grad_sumsq_parts",
+                           "rnvp_link_nclass", "rnvp_conv2d_check", "rnvp_conv2d_family", "rnvp_wgrad_class", "rnvp_wgrad_multi_plan", "rnvp_wgrad_multi_struct_size",
+                           "rnvp_grad_sumsq_parts",
                            "rnvp_weight_norm_tiles", "rnvp_weight_norm_opt_blocks",
                            "rnvp_net_group_prepare") or res is not i32
             setattr(self, name[len("rnvp_"):], fn if raw else self._wrap(name, fn))
@@ -241,6 +258,10 @@ class _Lib:
             if self.dll.rnvp_struct_size(i) != C.sizeof(m):
                 raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"
                                    % (path, m.__name__, self.dll.rnvp_struct_size(i), C.sizeof(m)))
+        for i, m in enumerate((WgradMultiConv, WgradMulti)):    # (rnvp_struct_size's list is closed)
+            if self.dll.rnvp_wgrad_multi_struct_size(i) != C.sizeof(m):
+                raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"
+                                   % (path, m.__name__, self.dll.rnvp_wgrad_multi_struct_size(i), C.sizeof(m)))
 
     def _wrap(self, name, fn):
         dll = self.dll

@@ -18,8 +18,9 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from ._lib import (BNBwdArgs, BNRunning, BNSrc, ConvArgs, CouplingArgs, NetStep, WgradConv, WgradGroup, WNDesc,
-                   bn_tab_floats, NET_GROUP_MAX, RNVP_BF16, RNVP_F32, RNVP_STEP_BN_BWD, RNVP_STEP_CONV, WGRAD_GROUP_MAX)
+from ._lib import (BNBwdArgs, BNRunning, BNSrc, ConvArgs, CouplingArgs, NetStep, WgradConv, WgradGroup, WgradMulti,
+                   WgradMultiConv, WNDesc, bn_tab_floats, NET_GROUP_MAX, RNVP_BF16, RNVP_F32, RNVP_STEP_BN_BWD,
+                   RNVP_STEP_CONV, WGRAD_GROUP_MAX)
 from .net import backward_program, build_program, chan_stride, round_up
 
 BN_EPS = 1e-5
@@ -45,6 +46,14 @@ FOLD_BN = True
 # instead of each workgroup re-deriving it from the sharded sums; False keeps
 # the shard reduction everywhere (A/B runs, tests)
 BN_TABLES = True
+# The deep couplings' weight gradients (bf16 groups that take the single
+# all-class launch, nrep == nz) are handed to the trainer, which runs them as
+# ONE launch per tile class over every such coupling after the last coupling's
+# backward (rnvp_conv2d_wgrad_multi; single-process opt="defer" schedule on the
+# main stream only: config 1 bf16 18.71 -> 18.45 ms per step,
+# profiles/wgrad_multi_ab.txt).  False keeps one launch per coupling (tests
+# compare the two: dW is bit-identical)
+WGRAD_MULTI = True
 
 
 def stream_ptr():
@@ -95,6 +104,37 @@ def _launch(family, nbytes, flops, fn, *args):
         PROFILE.append((family, nbytes, flops, e0, e1))
     if MARKERS:
         _lib.lib().marker(-1, stream_ptr())
+
+
+def plan_wgrad_multi(groups, device):
+    """The model-wide weight-gradient launches over `groups` (WgradGroup list):
+    [(WgradMulti, uploaded tables)] with one entry per tile class present, or
+    None when the library declines the list (rnvp_wgrad_multi_plan).  Host
+    only; the launches consume the uploaded plan."""
+    L = _lib.lib()
+    arr = (WgradGroup * len(groups))()
+    for i, g in enumerate(groups):
+        C.memmove(C.addressof(arr[i]), C.addressof(g), C.sizeof(WgradGroup))
+    out = []
+    for cls in range(4):
+        m = WgradMulti()
+        if L.wgrad_multi_plan(arr, len(groups), cls, None, 0, None, None, 0, C.byref(m)) != 0:
+            return None
+        if m.n_conv == 0:
+            continue
+        convs = (WgradMultiConv * m.n_conv)()
+        xs = (C.c_int * 9)()
+        tasks = (C.c_int * (2 * m.n_task))()
+        if L.wgrad_multi_plan(arr, len(groups), cls, convs, m.n_conv, xs, tasks, m.n_task, C.byref(m)) != 0:
+            return None
+        # one upload: convs | xcd_start (padded to 64 B) | tasks
+        raw = bytes(convs)
+        o_x = round_up(len(raw), 64)
+        raw += b"\0" * (o_x - len(raw)) + bytes(xs) + b"\0" * (64 - 36) + bytes(tasks)
+        t = upload(raw, device)
+        m.convs, m.xcd_start, m.tasks = t.data_ptr(), t.data_ptr() + o_x, t.data_ptr() + o_x + 64
+        out.append((m, t))
+    return out
 
 
 class Arena:
@@ -725,9 +765,28 @@ class CouplingEngine:
                 fl = sum(items[i][3] for i in range(i0, i1))
                 _launch("conv_dgrad", nb, fl, L.net_group, C.addressof(tab), i1 - i0, dt, klass, grid, lds, s)
 
-    def _weight_grads(self, sv, sc, ws, zero_at_end, opt, after, gbase):
+    def _wgrad_multi_ok(self, sv, sc, groups, multi):
+        """This coupling's groups can join the trainer's model-wide launch:
+        the library admits each of them (bf16, the single all-class launch,
+        plain stores) and no other deferred coupling shares this scratch."""
+        if not WGRAD_MULTI or sv["dtype"] != "bf16" or any(it[4] == id(sc) for it in multi):
+            return False
+        key = sv["bwd_plan"][0]
+        ok = sv.get("wg_multi_ok")
+        if ok is None or ok[0] != key:
+            L = _lib.lib()
+            m = WgradMulti()
+            ok = (key, all(L.wgrad_multi_plan(C.byref(g), 1, 0, None, 0, None, None, 0, C.byref(m)) == 0
+                           for g in groups))
+            sv["wg_multi_ok"] = ok
+        return ok[1]
+
+    def _weight_grads(self, sv, sc, ws, zero_at_end, opt, after, gbase, multi=None):
         """The closure issuing the net's grouped weight gradients (+ the
-        weight-norm backward or the fused parameter pass, see backward)."""
+        weight-norm backward or the fused parameter pass, see backward).
+        multi (opt="defer" only): the trainer's list of deferred groups --
+        an admitted coupling appends (groups, bytes, flops, plan key, scratch
+        id) instead of launching (WGRAD_MULTI)."""
         L = _lib.lib()
         ar, sar = sv["arena"], sc["arena"]
         z0, z1 = sc["zero"]
@@ -742,9 +801,14 @@ class CouplingEngine:
         # optimizer update).
         def weight_grads():
             ss = stream_ptr()
-            for grp in groups:
-                _launch("conv_wgrad", wg_bytes / len(groups), wg_flops / len(groups), L.conv2d_wgrad_grouped,
-                        C.byref(grp), ss)
+            if multi is not None and opt == "defer" and self._wgrad_multi_ok(sv, sc, groups, multi):
+                # this coupling's saved arena and gradient scratch are its
+                # own and persistent: nothing later in the step rewrites them
+                multi.append((groups, wg_bytes, wg_flops, (sv["bwd_plan"][0], ar.base), id(sc)))
+            else:
+                for grp in groups:
+                    _launch("conv_wgrad", wg_bytes / len(groups), wg_flops / len(groups), L.conv2d_wgrad_grouped,
+                            C.byref(grp), ss)
             # the backward reductions live in the scratch shared by every
             # caller of this shape (trainer and drop-in autograd alike): it is
             # ALWAYS left zero, so whichever path runs next finds it clean
@@ -909,7 +973,7 @@ class CouplingEngine:
             e[0] = "folded"
 
     def backward(self, sv, gz, gl_full, gl_sample, grad_block, gx=None, side=None, after=None, zero_at_end=False,
-                 defer=None, opt=None, reverse=False):
+                 defer=None, opt=None, reverse=False, multi=None):
         """Returns dL/dx; parameter gradients are written into grad_block
         (flat fp32, zeroed by the caller; scale/shift grads accumulate).
 
@@ -934,6 +998,10 @@ class CouplingEngine:
         new norms and the next step's packed images); "defer": only the
         weight gradients run here -- the caller runs the parameter pass over
         this coupling's slabs later (param_pass_info) and zeroes its sums.
+
+        multi: with opt="defer" on the main stream, the caller's list that
+        collects this coupling's weight-gradient groups for one model-wide
+        launch (WGRAD_MULTI, _weight_grads) instead of launching them here.
 
         reverse: sv comes from reverse(..., saved=sv): the backward of the
         inverse pass (rnvp_coupling_reverse_bwd in place of the out part's
@@ -987,7 +1055,8 @@ class CouplingEngine:
         _launch("coupling", 16 * n_el + 2 * esz * B * H * W * a.cs_gh0, 0.0, L.coupling_in_bwd, C.byref(a), s)
 
         # ... while the weight gradients only feed the optimizer
-        self._issue_weight_grads(self._weight_grads(sv, sc, ws, zero_at_end, opt, after, gbase), defer, side)
+        self._issue_weight_grads(self._weight_grads(sv, sc, ws, zero_at_end, opt, after, gbase,
+                                                    multi if side is None else None), defer, side)
         return gx
 
     @staticmethod
@@ -1067,7 +1136,7 @@ class CouplingEngine:
             _launch("coupling", nb, 0.0, L.coupling_link_fwd, C.byref(a), None, C.byref(link["args"]), s)
         sv["x"] = x
 
-    def backward_link(self, sv, link, grad_block, gx, gl_sample, first, defer, opt=None, after=None):
+    def backward_link(self, sv, link, grad_block, gx, gl_sample, first, defer, opt=None, after=None, multi=None):
         """Training backward of this coupling inside the trainer's flow program
         (after the consumer's): the link backward (dL/dz from the consumer's
         direct gradient + its in_bn backward, or the prior; then this coupling's
@@ -1076,7 +1145,8 @@ class CouplingEngine:
         dL/dx of the flow input).  gx receives this coupling's direct input
         gradient (the full dL/dx for the first).  The weight-gradient closure
         goes to `defer`: the caller runs it once the previous link's backward
-        has read this coupling's sums (the weight-norm backward zeroes them)."""
+        has read this coupling's sums (the weight-norm backward zeroes them).
+        multi: as in backward."""
         L = _lib.lib()
         x = sv["x"]
         B, H, W, dtype = sv["B"], sv["H"], sv["W"], sv["dtype"]
@@ -1108,4 +1178,4 @@ class CouplingEngine:
         cs_h0 = chan_stride(self.P.buf_ch["h0"])
         _launch("coupling", (8 if first else 4) * n_el + (2 if first else 1) * esz * B * H * W * cs_h0, 0.0,
                 L.coupling_in_bwd, C.byref(a), s)
-        self._issue_weight_grads(self._weight_grads(sv, sc, ws, True, opt, after, gbase), defer, None)
+        self._issue_weight_grads(self._weight_grads(sv, sc, ws, True, opt, after, gbase, multi), defer, None)

@@ -166,6 +166,11 @@ class FlowTrainer:
         # critical path (the forward/data-gradient chain)
         self.overlap = overlap
         self.side = torch.cuda.Stream(device=self.dev) if overlap else None
+        # the deep couplings' weight-gradient groups of the running step, handed
+        # over by their backward for the model-wide launch (engine.WGRAD_MULTI),
+        # and the cached plans: key -> ([(WgradMulti, uploaded tables)] or None, groups)
+        self._wg_multi = []
+        self._wg_multi_plans = {}
         if param_pass not in (None, "fused", "separate"):
             raise ValueError("param_pass must be None (fused when possible), 'fused' or 'separate'")
         self._build_param_pass("separate" if param_pass == "separate" else "fused")
@@ -804,7 +809,7 @@ class FlowTrainer:
                     after = (lambda lo=lo, hi=hi: self._adam_range(lo, hi))
                 opt = "defer" if self._slab_table is not None else None
                 eng.backward(sv, self._g(z), None, self.g_lp, block, gx=self._g(x), side=self.side, after=after,
-                             zero_at_end=True, opt=opt)
+                             zero_at_end=True, opt=opt, multi=self._multi_list(opt))
                 self._issue_buckets(ci, n_coupling)
             elif st[0] == "squeeze":
                 _, a, b = st
@@ -834,10 +839,51 @@ class FlowTrainer:
         for k in reversed(range(n_coupling)):
             _, mod, eng, x, z, sv, block = self.stages[self.cidx[k]]
             mine = []
-            eng.backward_link(sv, self.link_bwd[k], block, self._g(x), self.g_lp, k == 0, mine, opt=opt)
+            eng.backward_link(sv, self.link_bwd[k], block, self._g(x), self.g_lp, k == 0, mine, opt=opt,
+                              multi=self._multi_list(opt))
             self._run_pending(pending, pending_ci, n_coupling)
             pending, pending_ci = mine, k
         self._run_pending(pending, pending_ci, n_coupling)
+
+    def _multi_list(self, opt):
+        """The list that collects the couplings' weight-gradient groups for
+        the model-wide launch: the single-process deferred parameter pass on
+        the main stream only (data-parallel, clipping, accumulation and
+        --overlap schedules keep every coupling's own launch)."""
+        from . import engine
+        return self._wg_multi if engine.WGRAD_MULTI and opt == "defer" and self.side is None else None
+
+    def _wgrad_multi(self):
+        """The weight gradients the couplings' backwards handed over
+        (engine.WGRAD_MULTI): one launch per tile class over all of them,
+        after the last coupling's backward and before the parameter pass that
+        first reads their slabs (merging per run of same-shape couplings
+        instead, while their operands are still in the last-level cache,
+        measured 0.10 ms per step slower: profiles/wgrad_multi_ab.txt).  The
+        plan is built once and rebuilt when a coupling's backward plan or
+        scratch changes."""
+        items = self._wg_multi
+        if not items:
+            return
+        from . import engine
+        L = _lib.lib()
+        s = stream_ptr()
+        key = tuple((it[3], it[4]) for it in items)
+        if key not in self._wg_multi_plans:
+            if len(self._wg_multi_plans) >= 16:     # (stale keys: a backward plan or a scratch was rebuilt)
+                self._wg_multi_plans.clear()
+            groups = [g for it in items for g in it[0]]
+            self._wg_multi_plans[key] = (engine.plan_wgrad_multi(groups, self.dev), groups)
+        plan, groups = self._wg_multi_plans[key]
+        nb, fl = sum(it[1] for it in items), sum(it[2] for it in items)
+        if plan is None:
+            # the library declines the combined list: every group's own launch
+            for g in groups:
+                _launch("conv_wgrad", nb / len(groups), fl / len(groups), L.conv2d_wgrad_grouped, C.byref(g), s)
+        else:
+            for m, _ in plan:
+                _launch("conv_wgrad", nb / len(plan), fl / len(plan), L.conv2d_wgrad_multi, C.byref(m), s)
+        items.clear()
 
     def _run_pending(self, pending, ci, n_coupling):
         if not pending:
@@ -934,7 +980,9 @@ class FlowTrainer:
         else:
             self.grad.zero_()
         self._forward()
+        del self._wg_multi[:]
         self._backward()
+        self._wgrad_multi()
         if self.side is not None:
             torch.cuda.current_stream().wait_stream(self.side)
         if self.comm_stream is not None:

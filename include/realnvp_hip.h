@@ -38,7 +38,9 @@ int rnvp_version(void);
  * rnvp_bn_bwd_args, rnvp_wn_desc, rnvp_adam_args, rnvp_coupling_args,
  * rnvp_net_step, rnvp_range, rnvp_link_args, rnvp_step_ctl (-1 past the end).  A binding compares them with
  * its own mirrors at load time: a library built from another header revision
- * is refused instead of reading descriptor tables at the wrong stride. */
+ * is refused instead of reading descriptor tables at the wrong stride.  (The
+ * list is closed: later structs report their size next to their entry points,
+ * see rnvp_wgrad_multi_struct_size.) */
 int rnvp_struct_size(int which);
 const char* rnvp_status_string(int status);
 /* empty one-lane dispatch: delimits engine launches in PMC traces (profiling only) */
@@ -242,6 +244,52 @@ int rnvp_conv2d_wgrad_grouped(const rnvp_wgrad_group* g, void* stream);
  * channels, 3: 1x1 up to 64), RNVP_E_UNSUPPORTED when the group takes the
  * generic kernel */
 int rnvp_wgrad_class(const rnvp_wgrad_group* g, int c);
+
+/* model-wide weight gradient: the tap-shared bf16 tiles of MANY groups (the
+ * deep couplings, whose own launches are each short of work) in one launch per
+ * tile class, driven by device-resident tables instead of the by-value group.
+ * A table entry is a conv with its own shape and class; the block -> task map
+ * is planned on the host once (rnvp_wgrad_multi_plan) and uploaded:
+ *   xcd_start[9]      task-list offsets per XCD (block b serves XCD b % 8 and
+ *                     takes entry b / 8 of that XCD's list; surplus blocks exit)
+ *   tasks[n_task][2]  {conv index, local tile id = (slab * co tiles + co tile)
+ *                     * ci tiles + ci tile}
+ * The (conv, slab) runs are split over the XCDs by summed cost (stages +
+ * a per-workgroup overhead per tile), longest first onto the least loaded
+ * XCD; a run's tiles stay adjacent on one XCD (they share the slab's pixels
+ * through L2) and every XCD's list is ordered by descending tile cost.
+ * Only plain-store convs (nrep == nz) are admitted: every float of ws / wsb
+ * is then what the group's own rnvp_conv2d_wgrad_grouped launch writes. */
+typedef struct rnvp_wgrad_multi_conv {
+    const void* x; const void* dy; float* ws; float* wsb;
+    rnvp_bn_src pro;
+    int cs_in, cin, cs_dy, n, kp, pro_bn_relu, nz, nrep;
+    int B, H, W, cls;
+    int tco, tci;                       /* co / ci tiles of the class */
+    long long m_per_slab;
+} rnvp_wgrad_multi_conv;
+typedef struct rnvp_wgrad_multi {
+    int cls, ko, n_conv, n_task, grid, lds_bytes;   /* filled by the planner */
+    long long xcd_cost[8];                          /* filled by the planner */
+    /* device copies of the planner's arrays, set by the caller after upload */
+    const rnvp_wgrad_multi_conv* convs;
+    const int* xcd_start;
+    const int* tasks;
+} rnvp_wgrad_multi;
+/* host only, nothing launched: the plan of class cls (0 .. 3) over the groups'
+ * convs of that class.  convs (conv_cap entries), xcd_start (9 ints) and tasks
+ * (2 * task_cap ints) receive the arrays to upload; with convs == NULL only
+ * the counts (m->n_conv, m->n_task) are filled.  m->n_conv == 0: the class is
+ * absent, nothing to launch.  RNVP_E_UNSUPPORTED: a group is not bf16, is
+ * declined by the tap-shared kernel, holds a conv with nrep < nz, or would
+ * run in another k order than its own launch (the caller keeps that group's
+ * own launch); RNVP_E_INVALID: bad arguments or capacities. */
+int rnvp_wgrad_multi_plan(const rnvp_wgrad_group* groups, int n_groups, int cls, rnvp_wgrad_multi_conv* convs,
+                          int conv_cap, int* xcd_start, int* tasks, int task_cap, rnvp_wgrad_multi* m);
+int rnvp_conv2d_wgrad_multi(const rnvp_wgrad_multi* m, void* stream);
+/* sizeof rnvp_wgrad_multi_conv (0) and rnvp_wgrad_multi (1), -1 otherwise: a
+ * binding compares them with its mirrors at load, as with rnvp_struct_size */
+int rnvp_wgrad_multi_struct_size(int which);
 
 /* batch-norm backward apply (train mode), the second half of BN backward:
  * dx = gamma*rstd*(g - sum_g/M - xhat * sum_gxhat/M) (+ residual) (+= dx if accumulate)
