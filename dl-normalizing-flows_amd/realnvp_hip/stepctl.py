@@ -7,7 +7,9 @@ device-resident ``rnvp_step_ctl`` block; ``rnvp_step_control`` evaluates the
 schedule there from the optimizer's step counter, so a captured step follows
 it without re-capture.  With ``accum_steps = K > 1`` the same block counts
 the micro-steps of the open optimizer step (``micro``) and decides on the
-device which replay holds and which applies.
+device which replay holds and which applies.  A FlowTrainer built with
+``ema_decay`` keeps the exponential moving average of its parameters with a
+block of its own (``rnvp_ema_ctl``); ``ema_decay_at`` mirrors its decay.
 """
 import math
 
@@ -110,3 +112,27 @@ def fill_ctl(ctl, base_lr, schedule, max_grad_norm, accum_steps=1):
     ctl.max_norm = max_grad_norm if max_grad_norm is not None else 0.0
     ctl.accum_steps = check_accum_steps(accum_steps)
     return ctl
+
+
+def check_ema_decay(v):
+    """None (no weight averaging) or a decay 0 <= v < 1"""
+    if v is None:
+        return None
+    try:
+        if isinstance(v, (bool, str, bytes)):
+            raise TypeError
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("ema_decay must be a number in [0, 1) or None, got %r" % (v,)) from None
+    if not (0.0 <= v < 1.0):
+        raise ValueError("ema_decay must be in [0, 1) or None, got %r" % (v,))
+    return v
+
+
+def ema_decay_at(decay, warmup, u):
+    """float64 mirror of rnvp_ema_update's decay (include/realnvp_hip.h,
+    "weight averaging") at the u-th optimizer step, u = 1, 2, ...: with
+    warm-up min(decay, (1 + u) / (10 + u)), which reaches 0.999 at u = 8990;
+    the average then is e + (1 - d) (p - e)."""
+    decay, u = float(decay), int(u)
+    return min(decay, (1.0 + u) / (10.0 + u)) if warmup else decay

@@ -32,7 +32,13 @@ MI355X-specific structure:
     their bits -- and the K-th leaves the average in the gradient arena,
     decides on it and applies.  The dequantisation noise then has a counter
     of its own, which moves every micro-step.
+  * optional weight averaging (ema_decay=d): an fp32 arena laid out like the
+    parameters holds their exponential moving average; one launch after the
+    step's last Adam launch (rnvp_ema_update) moves it, inside the captured
+    step, and follows the device's skip / hold decisions.  ema_weights()
+    exchanges the two arenas in place for evaluation and sampling.
 """
+import contextlib
 import ctypes as C
 import gc
 import math
@@ -111,13 +117,14 @@ class FlowTrainer:
     def __init__(self, model, batch_size, lr=5e-4, weight_decay=5e-5, betas=(0.9, 0.999), eps=1e-8,
                  scale_reg=5e-5, dtype="bf16", seed=0, process_group=None, bucket_mb=25, overlap=False,
                  comm="overlap", reduce_dtype="fp32", param_pass=None, chain=True, max_grad_norm=None,
-                 lr_schedule=None, accum_steps=1):
-        from .stepctl import StepSchedule, check_accum_steps, check_max_grad_norm
+                 lr_schedule=None, accum_steps=1, ema_decay=None, ema_warmup=True):
+        from .stepctl import StepSchedule, check_accum_steps, check_ema_decay, check_max_grad_norm
         if lr_schedule is not None and not isinstance(lr_schedule, StepSchedule):
             raise ValueError("lr_schedule must be a realnvp_hip.stepctl.StepSchedule or None")
         self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.lr_schedule = lr_schedule
         self.accum_steps = check_accum_steps(accum_steps)
+        self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
         if self.accum_steps > 1 and process_group is not None:
             raise ValueError("accum_steps > 1 with a process_group is not supported: every micro-step would "
                              "all-reduce (deferring it to the last one is not built)")
@@ -144,6 +151,7 @@ class FlowTrainer:
         model.train()
         self._build_arenas()
         self._build_step_control()
+        self._build_ema()
         self._build_plan(chain)
         self.graph = None
         self.graph_opt = None
@@ -330,6 +338,118 @@ class FlowTrainer:
         """the Philox counter of the dequantisation noise: the step counter,
         or the micro-step counter of an accumulating trainer"""
         return (self.noise_t if self.noise_t is not None else self.step_t).data_ptr()
+
+    # -------------------------------------------------------- weight averaging
+    def _build_ema(self):
+        """The average's arena (laid out like self.param, a copy of it to
+        begin with) and its device-resident rnvp_ema_ctl block (include/
+        realnvp_hip.h, "weight averaging") of a trainer built with ema_decay;
+        nothing otherwise.  BatchNorm running statistics are buffers, and
+        averages already: they are not part of it."""
+        self.ema = self.ema_buf = None
+        self._ema_in = False        # inside ema_weights(): the two arenas are exchanged
+        if self.ema_decay is None:
+            return
+        from ._lib import EmaCtl
+        from .engine import upload
+        self.ema = self.param.clone()
+        self.ema_buf = upload(bytes(EmaCtl(self.ema_decay, int(self.ema_warmup), 0.0, 0, 0)), self.dev)
+
+    def _ema_field(self, name):
+        """a one-element tensor view of a field of the average's block"""
+        from ._lib import EmaCtl
+        f = getattr(EmaCtl, name)
+        dt = {C.c_float: torch.float32, C.c_int: torch.int32, C.c_longlong: torch.int64}[dict(EmaCtl._fields_)[name]]
+        return self.ema_buf[f.offset:f.offset + f.size].view(dt)
+
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError("%s needs a FlowTrainer built with ema_decay" % what)
+
+    def _not_swapped(self, what):
+        if self._ema_in:
+            raise RuntimeError("%s inside ema_weights(): the parameters hold the average" % what)
+
+    def set_ema_decay(self, d):
+        """The average's decay from the next step on: a stream-ordered write
+        into its block, no re-capture."""
+        from .stepctl import check_ema_decay
+        self._need_ema("set_ema_decay")
+        if d is None:
+            raise ValueError("ema_decay must be in [0, 1), got None (weight averaging is fixed at construction)")
+        self.ema_decay = check_ema_decay(d)
+        self._ema_field("decay").fill_(self.ema_decay)
+
+    def ema_state(self):
+        """decay and warmup as configured, applied (the decay the last applied
+        update used) and n_updates (updates applied: skipped and held steps
+        do not count).  Synchronises (a device-to-host copy)."""
+        self._need_ema("ema_state")
+        from ._lib import EmaCtl
+        c = EmaCtl.from_buffer_copy(bytes(self.ema_buf.cpu().numpy()))
+        return {"decay": c.decay, "warmup": bool(c.warmup), "applied": c.applied, "n_updates": int(c.n_updates)}
+
+    def reset_ema(self):
+        """The average becomes the current parameters and n_updates 0: after
+        the caller has written the parameters itself (an initialisation, a
+        model.load_state_dict)."""
+        self._need_ema("reset_ema")
+        self._not_swapped("reset_ema")
+        with torch.no_grad():
+            self.ema.copy_(self.param)
+        self._ema_field("n_updates").fill_(0)
+
+    def _ema_update(self, step_add):
+        """the step's one averaging launch, after its last Adam launch;
+        step_add: 1 while the step counter has not moved yet, 0 after"""
+        if self.ema is None:
+            return
+        _launch("param", 12 * self.n, 0.0, _lib.lib().ema_update, self.ema.data_ptr(), self.param.data_ptr(), self.n,
+                self.ema_buf.data_ptr(), self.step_t.data_ptr(), step_add,
+                self.ctl_buf.data_ptr() if self.ctl_buf is not None else None, stream_ptr())
+
+    def _ema_swap(self):
+        _lib.lib().ema_swap(self.param.data_ptr(), self.ema.data_ptr(), self.n, stream_ptr())
+        self.invalidate_packed()
+
+    def ema_state_dict(self):
+        """model.state_dict()'s keys and shapes, cloned: the parameters from
+        the average, the buffers as they are.  Loads into another RealNVP (or
+        the reference's)."""
+        self._need_ema("ema_state_dict")
+        avg = self.param if self._ema_in else self.ema
+        shapes = dict(self.model.named_parameters())
+        out = {}
+        for k, v in self.model.state_dict().items():
+            if k in shapes:
+                off = self.offsets[k]
+                out[k] = avg[off:off + v.numel()].view_as(v).clone()
+            else:
+                out[k] = v.detach().clone()
+        return out
+
+    def ema_weights(self):
+        """with tr.ema_weights(): the model's parameters hold the average
+        (rnvp_ema_swap exchanges the two arenas in place -- no pointer moves,
+        no temporary), so FlowEvaluator, FlowSampler and the drop-in modules,
+        which derive their packed weight images from the parameters on every
+        pass, evaluate and sample from it.  Leaving the block (an exception
+        included) exchanges them back, and the next step re-derives the
+        training images.  step(), step_eager(), capture() and the checkpoint
+        methods raise inside the block; it is not re-entrant."""
+        self._need_ema("ema_weights")
+        return self._ema_swapped()
+
+    @contextlib.contextmanager
+    def _ema_swapped(self):
+        self._not_swapped("ema_weights")
+        self._ema_swap()
+        self._ema_in = True
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+            self._ema_in = False
 
     # ------------------------------------------------------------------- plan
     def _build_plan(self, chain=True):
@@ -945,21 +1065,26 @@ class FlowTrainer:
                 _launch("param", tb / len(self.wn_tables), 0.0, L.weight_norm_transpose, t.data_ptr(), n, tiles, dt,
                         s)
             L.adam_gather(C.byref(self._opt_all), self._opt_rest.data_ptr(), self._opt_rest.numel(), s)
+            self._ema_update(1)
             self._advance_step()
             return
         if self.adam_ranges is not None:
-            # the per-coupling updates already ran (side stream, t = step + 1)
+            # the per-coupling updates already ran (side stream, t = step + 1;
+            # _fwd_bwd has made this stream wait for them)
+            self._ema_update(1)
             self._advance_step()
             return
         if self.ctl_buf is not None:
             # rnvp_adam_step's update (t = step + 1) under the step control
             _lib.lib().adam_range(C.byref(self._opt_all), self.n, stream_ptr())
+            self._ema_update(1)
             self._advance_step()
             return
         b1, b2 = self.betas
         _lib.lib().adam_step(self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
                              self.exp_avg_sq.data_ptr(), self.n, self.step_t.data_ptr(), self.lr, b1, b2, self.eps,
                              self.wd, self.mask.data_ptr(), self.reg, stream_ptr())
+        self._ema_update(0)     # (rnvp_adam_step's first kernel has moved the counter)
 
     def _allreduce(self):
         """Whole-arena bucketed average ("split" mode: between the captured
@@ -989,6 +1114,7 @@ class FlowTrainer:
             torch.cuda.current_stream().wait_stream(self.comm_stream)
 
     def step_eager(self):
+        self._not_swapped("step_eager()")
         self._ensure_packed()
         self._fwd_bwd()
         self._allreduce()
@@ -999,12 +1125,16 @@ class FlowTrainer:
         bufs = {n: b.detach().clone() for n, b in self.model.named_buffers()}
         ctl = self.ctl_buf.clone() if self.ctl_buf is not None else None
         accum = (self.acc.clone(), self.noise_t.clone()) if self.acc is not None else None
+        ema = (self.ema.clone(), self.ema_buf.clone()) if self.ema is not None else None
         return (self.param.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.step_t.clone(),
-                self.ll_acc.clone(), bufs, ctl, accum)
+                self.ll_acc.clone(), bufs, ctl, accum, ema)
 
     def _restore(self, snap):
-        p, m, v, t, ll, bufs, ctl, accum = snap
+        p, m, v, t, ll, bufs, ctl, accum, ema = snap
         with torch.no_grad():
+            if ema is not None:
+                self.ema.copy_(ema[0])
+                self.ema_buf.copy_(ema[1])  # the warm-up steps' n_updates
             if ctl is not None:
                 self.ctl_buf.copy_(ctl)     # the warm-up steps' counters (and micro)
             if accum is not None:
@@ -1050,6 +1180,7 @@ class FlowTrainer:
         if self.pg is not None and not restore:
             raise ValueError("with a process group, capture() must restore the warm-up state: its warm-up "
                              "steps issue no all-reduce (see capture)")
+        self._not_swapped("capture()")
         snap = self._snapshot() if restore else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -1114,6 +1245,7 @@ class FlowTrainer:
         self.graph = self.graph_opt = self.graph_input = None
 
     def step(self):
+        self._not_swapped("step()")
         if self.graph is None:
             return self.step_eager()
         self._ensure_packed()
@@ -1228,7 +1360,10 @@ class FlowTrainer:
         stays in the optimizer's param_groups[0]['lr']), accum_steps and
         micro, and -- taken between the micro-steps of one optimizer step,
         micro > 0 -- the gradient accumulator, so that the resumed run
-        completes that step bit for bit."""
+        completes that step bit for bit.  A trainer with weight averaging
+        adds 'ema': decay, warmup, n_updates and 'shadow', a clone of the
+        average's arena."""
+        self._not_swapped("state_dict()")
         sd = {"model": self.model.state_dict(), "optimizer": self.optimizer_state_dict(),
               "rng": self.rng_state()}
         if self.ctl_buf is not None:
@@ -1239,7 +1374,27 @@ class FlowTrainer:
                                   "micro": st["micro"]}
             if st["micro"] > 0:
                 sd["step_control"]["accum"] = self.acc.clone()
+        if self.ema is not None:
+            sd["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup,
+                         "n_updates": self.ema_state()["n_updates"], "shadow": self.ema.clone()}
         return sd
+
+    def _load_ema(self, e):
+        """the checkpoint's average, or -- a checkpoint without one -- the
+        parameters just loaded"""
+        if e is None:
+            self.reset_ema()
+            return
+        shadow = e["shadow"].reshape(-1)
+        if shadow.numel() != self.n:
+            raise ValueError("the checkpoint's average has %d elements, the parameter arena %d"
+                             % (shadow.numel(), self.n))
+        self.set_ema_decay(e["decay"])
+        self.ema_warmup = bool(e["warmup"])
+        self._ema_field("warmup").fill_(int(self.ema_warmup))
+        self._ema_field("n_updates").fill_(int(e["n_updates"]))
+        with torch.no_grad():
+            self.ema.copy_(shadow)
 
     def _load_step_control(self, sc):
         from .stepctl import StepSchedule, check_max_grad_norm
@@ -1275,11 +1430,17 @@ class FlowTrainer:
         if k != self.accum_steps:
             raise ValueError("the checkpoint was taken with accum_steps=%d, this FlowTrainer was built with "
                              "accum_steps=%d" % (k, self.accum_steps))
+        self._not_swapped("load_state_dict()")
+        if sd.get("ema") is not None and self.ema is None:
+            raise ValueError("the checkpoint carries averaged weights (ema_decay=%r); build the FlowTrainer with "
+                             "ema_decay to resume it" % (sd["ema"]["decay"],))
         with torch.no_grad():
             self.model.load_state_dict(sd["model"])
         self.load_optimizer_state_dict(sd["optimizer"])
         if sc is not None:
             self._load_step_control(sc)
+        if self.ema is not None:
+            self._load_ema(sd.get("ema"))
         rng = sd.get("rng")
         if rng is not None:
             # a checkpoint of THIS rank resumes its noise stream exactly; one

@@ -661,6 +661,53 @@ int rnvp_step_control(rnvp_step_ctl* ctl, const long long* step, const double* p
 int rnvp_adam_range(const rnvp_adam_args* ad, long long n, void* stream);
 int rnvp_step_advance(long long* step, const rnvp_step_ctl* ctl, void* stream);
 
+/* ---- weight averaging ------------------------------------------------------
+ * The exponential moving average (Polyak average) of the parameter arena, kept
+ * by the training step: one launch of its own after the step's last Adam
+ * launch, with a device-resident control block of its own (rnvp_adam_args,
+ * rnvp_step_ctl and the Adam kernels know nothing of it).
+ *
+ * rnvp_ema_update, one pass over the arena (12 B / element):
+ *   u = *step + step_add   the optimizer steps taken, this one included
+ *                          (step_add = 1 before the counter has moved, 0 after)
+ *   d = warmup ? fminf(decay, (1 + u) / (10 + u)) : decay       in fp32
+ *   e' = e + (1 - d) * (p - e)
+ * as three separately rounded IEEE fp32 operations (a subtraction, a
+ * multiplication by the fp32 value 1 - d, an addition; never an fma), so an
+ * element with p == e keeps its value (and, but for a negative zero, its
+ * bits): frozen parameters and the arena's padding need no mask.  d == 0
+ * (a decay of 0: no averaging) stores p itself.  With ctl !=
+ * NULL and ctl->skip set (a skipped step, or a held micro-step of an
+ * accumulating block) the kernel returns before it loads an element and
+ * writes nothing, ectl included.  Otherwise one thread stores applied = d and
+ * n_updates + 1 with plain stores; no other thread reads a field the kernel
+ * writes.  With warm-up off this is torch.optim.swa_utils.
+ * get_ema_multi_avg_fn(decay): ema.lerp_(p, 1 - decay).
+ * The host writes decay / warmup with stream-ordered copies (0 <= decay < 1 is
+ * the writer's responsibility: the library does not read the block on the
+ * host).
+ *
+ * rnvp_ema_swap exchanges two arenas in place (16 B / element): evaluation
+ * reads the average through the parameters' own storage, with no temporary.
+ *
+ * Both are stream-ordered and capture-safe, use no LDS and no atomics, and
+ * check their arguments before any HIP call: RNVP_E_INVALID for a NULL ema /
+ * param / ectl / step (a / b), n < 0 or n % 4 != 0, arenas that are not
+ * 16-byte aligned (ectl, step and ctl: 8-byte), or arenas that overlap
+ * (a == b included).  n == 0 is RNVP_OK with nothing launched. */
+typedef struct rnvp_ema_ctl {
+    float decay;            /* configuration, host-written */
+    int warmup;
+    float applied;          /* device: the decay the last applied update used */
+    int pad;
+    long long n_updates;    /* device: updates applied so far */
+} rnvp_ema_ctl;
+/* sizeof(rnvp_ema_ctl), for a binding's mirror (the list of rnvp_struct_size is closed) */
+int rnvp_ema_struct_size(void);
+int rnvp_ema_update(float* ema, const float* param, long long n, rnvp_ema_ctl* ectl, const long long* step,
+                    long long step_add, const rnvp_step_ctl* ctl /* may be NULL */, void* stream);
+int rnvp_ema_swap(float* a, float* b, long long n, void* stream);
+
 /* ---- net steps ------------------------------------------------------------
  * One s/t-net step as a table entry (rnvp_net_group): a conv (rnvp_conv2d
  * semantics) or a BatchNorm-backward apply (rnvp_bn_bwd_apply semantics).
