@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from modules_realnvp import ChannelwiseAffineCoupling, CheckerboardAffineCoupling
 from realnvp_hip import functions as Fn
+from realnvp_hip.program import flow_schedule, inverse_schedule, run_functional
 
 __all__ = ["RealNVP"]
 
@@ -121,72 +122,27 @@ class RealNVP(nn.Module):
         return getattr(self, "s%d_ckbd" % s), (getattr(self, "s%d_chan" % s) if s < self.n_scales else None)
 
     def f(self, x):
-        """flow_realnvp.py:252-327: x -> (z, elementwise log_diag_J)."""
-        z, ldj = x, torch.zeros_like(x)
-        offs = []
-        for s in range(1, self.n_scales):
-            ckbd, chan = self._scale_mods(s)
-            for m in ckbd:
-                z, inc = m(z)
-                ldj = ldj + inc
-            z, ldj = Fn.squeeze(z), Fn.squeeze(ldj)
-            for m in chan:
-                z, inc = m(z)
-                ldj = ldj + inc
-            z, ldj = Fn.undo_squeeze(z), Fn.undo_squeeze(ldj)
-            z, z_off = Fn.factor_out(z)
-            ldj, l_off = Fn.factor_out(ldj)
-            offs.append((z_off, l_off))
-        for m in self._scale_mods(self.n_scales)[0]:
+        """flow_realnvp.py:252-327: x -> (z, elementwise log_diag_J), which
+        takes every permutation z takes."""
+        def coupling(m, z, ldj):
             z, inc = m(z)
-            ldj = ldj + inc
-        for z_off, l_off in reversed(offs):
-            z = Fn.restore(z, z_off)
-            ldj = Fn.restore(ldj, l_off)
-        return z, ldj
+            return z, ldj + inc
+        return tuple(run_functional(flow_schedule(self), coupling, x, torch.zeros_like(x)))
 
     def _f_sample(self, x):
         """Hot path of log_prob: z plus the per-sample log-det sum [B]."""
-        z = x
         parts = []
-        offs = []
-        for s in range(1, self.n_scales):
-            ckbd, chan = self._scale_mods(s)
-            for m in ckbd:
-                z, l = Fn.coupling_apply(m, z, full_ldj=False)
-                parts.append(l)
-            z = Fn.squeeze(z)
-            for m in chan:
-                z, l = Fn.coupling_apply(m, z, full_ldj=False)
-                parts.append(l)
-            z = Fn.undo_squeeze(z)
-            z, z_off = Fn.factor_out(z)
-            offs.append(z_off)
-        for m in self._scale_mods(self.n_scales)[0]:
+
+        def coupling(m, z):
             z, l = Fn.coupling_apply(m, z, full_ldj=False)
             parts.append(l)
-        for z_off in reversed(offs):
-            z = Fn.restore(z, z_off)
+            return (z,)
+        z, = run_functional(flow_schedule(self), coupling, x)
         return z, torch.stack(parts, 0).sum(0)
 
     def g(self, z):
-        """flow_realnvp.py:196-249: z -> x (exact inverse)."""
-        x = z
-        offs = []
-        for s in range(1, self.n_scales):
-            x, off = Fn.factor_out(x)
-            offs.append(off)
-        for m in reversed(self._scale_mods(self.n_scales)[0]):
-            x, _ = m(x, reverse=True)
-        for s in reversed(range(1, self.n_scales)):
-            ckbd, chan = self._scale_mods(s)
-            x = Fn.restore(x, offs[s - 1])
-            x = Fn.squeeze(x)
-            for m in reversed(chan):
-                x, _ = m(x, reverse=True)
-            x = Fn.undo_squeeze(x)
-            for m in reversed(ckbd):
-                x, _ = m(x, reverse=True)
+        """flow_realnvp.py:196-249: z -> x (exact inverse): the inverse schedule."""
+        x, = run_functional(inverse_schedule(flow_schedule(self)), lambda m, x: (m(x, reverse=True)[0],), z)
         return x
 
     def log_prob(self, x):

@@ -5,6 +5,7 @@ Layout:
   net.py         the s/t ResNet as a conv program (forward + derived backward)
   engine.py      per-coupling executor (workspaces, kernel sequencing)
   functions.py   autograd Functions for the drop-in modules
+  program.py     the multi-scale flow as one schedule; its inverse is derived
   trainer.py     fused NLL training step (flat parameter arena, fused Adam,
                  HIP-graph capture, RCCL data parallelism)
   optim.py       FusedAdam: torch.optim.Adam drop-in for the reference loop

@@ -191,6 +191,41 @@ def wn_tiles(cout, cin, ks):
     return n
 
 
+def wn_table(engines, dtype, dev):
+    """One weight-norm descriptor table over the convs of several couplings
+    (rnvp_weight_norm_fwd refreshes all their packed weight images in two
+    launches: row norms, then both images on tiles).  None when there are no convs."""
+    descs = []
+    row0 = tile0 = 0
+    for eng in engines:
+        for d in eng.weights(dtype)["descs"]:
+            e = WNDesc()
+            C.memmove(C.addressof(e), C.addressof(d), C.sizeof(WNDesc))
+            e.row0, e.tile0 = row0, tile0
+            row0 += e.cout
+            tile0 += wn_tiles(e.cout, e.cin, e.ks)
+            descs.append(e)
+    if not descs:
+        return None
+    tab = (WNDesc * len(descs))(*descs)
+    t = upload(bytes(tab), dev)
+    return (t, len(descs), row0, tile0)
+
+
+def weights_key(engines, dtype):
+    """Identity of the packed-weight arenas of these couplings: changes when
+    a coupling's parameter storage moved (e.g. a FlowTrainer re-pointed the
+    parameters into its flat arena), which makes CouplingEngine.weights()
+    rebuild -- and free -- the arena a weight-norm table or a captured graph
+    points into."""
+    return tuple(e.weights(dtype)["key"] for e in engines)
+
+
+def wn_forward(table, dtype):
+    t, n, rows, tiles = table
+    _lib.lib().weight_norm_fwd(t.data_ptr(), n, rows, tiles, 1 if dtype == "bf16" else 0, stream_ptr())
+
+
 _SPLITK_WS = {}
 
 

@@ -18,8 +18,8 @@ import math
 import torch
 
 from . import _lib
-from .engine import stream_ptr
-from .trainer import weights_key, wn_forward, wn_table
+from .engine import stream_ptr, weights_key, wn_forward, wn_table
+from .program import FlowProgram, capture_graph, current_wn_table
 
 
 class FlowEvaluator:
@@ -34,72 +34,27 @@ class FlowEvaluator:
         C, S = model.channels, model.image_size
         f32 = dict(device=self.dev, dtype=torch.float32)
         self.pix = torch.zeros(batch_size, C, S, S, **f32)
-        self.xl = torch.empty_like(self.pix)
         self.logdet = torch.empty(batch_size, **f32)
         self.ldj = torch.zeros(batch_size, **f32)
         self.lp = torch.empty(batch_size, **f32)
         self.ll_sum = torch.zeros(1, dtype=torch.float64, device=self.dev)
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.n_batches = 0
-        self._plan(f32)
-        self.engines = list(dict.fromkeys(st[1].engine() for st in self.ops if st[0] == "coupling"))
+        # the forward flow program (program.py) in eval mode, per-sample log-det accumulation
+        self.program = FlowProgram(model, batch_size, self.dev, self.dtype, False)
+        self.xl, self.z = self.program.x, self.program.z
+        self.engines = list(dict.fromkeys(st.eng for st in self.program.couplings))
         self.table = wn_table(self.engines, self.dtype, self.dev)
         self._wkey = weights_key(self.engines, self.dtype)
         self.graph = None
         self.use_graph = graph
 
     def _check_weights(self):
-        """Rebuild the weight-norm table and drop the captured graph when the
-        parameters moved since they were built (their packed-weight arenas
-        were re-allocated): both hold raw arena pointers."""
-        k = weights_key(self.engines, self.dtype)
-        if k != self._wkey:
-            self.table = wn_table(self.engines, self.dtype, self.dev)
-            self._wkey = k
+        """The weight-norm table follows parameters that moved since it was
+        built; a graph captured with the old one is dropped."""
+        self.table, self._wkey, moved = current_wn_table(self.engines, self.dtype, self.dev, self._wkey, self.table)
+        if moved:
             self.graph = None
-
-    def _plan(self, f32):
-        """the op list of flow_realnvp.RealNVP.f (flow_realnvp.py:252-327) with
-        persistent buffers and per-sample log-det accumulation"""
-        m = self.model
-        B = self.B
-        ops = []
-        cur = self.xl
-        c, s = m.channels, m.image_size
-        offs = []
-
-        def coupling(mod, x):
-            eng = mod.engine()
-            sv = eng.alloc_saved(B, x.shape[2], x.shape[3], self.dtype, self.dev, False)
-            z = torch.empty_like(x)
-            ops.append(("coupling", mod, x, z, sv))
-            return z
-
-        for si in range(1, m.n_scales):
-            ckbd, chan = m._scale_mods(si)
-            for mod in ckbd:
-                cur = coupling(mod, cur)
-            sq = torch.empty(B, 4 * c, s // 2, s // 2, **f32)
-            ops.append(("squeeze", cur, sq))
-            cur = sq
-            for mod in chan:
-                cur = coupling(mod, cur)
-            un = torch.empty(B, c, s, s, **f32)
-            ops.append(("undo", cur, un))
-            on = torch.empty(B, 2 * c, s // 2, s // 2, **f32)
-            off = torch.empty_like(on)
-            ops.append(("factor_out", un, on, off))
-            offs.append(off)
-            cur = on
-            c, s = 2 * c, s // 2
-        for mod in m._scale_mods(m.n_scales)[0]:
-            cur = coupling(mod, cur)
-        for off in reversed(offs):
-            full = torch.empty(B, off.shape[1] // 2, off.shape[2] * 2, off.shape[3] * 2, **f32)
-            ops.append(("restore", cur, off, full))
-            cur = full
-        self.z = cur
-        self.ops = ops
 
     def _batch(self):
         L = _lib.lib()
@@ -109,40 +64,15 @@ class FlowEvaluator:
         L.logit_fwd(self.pix.data_ptr(), None, self.seed, 0, self.counter.data_ptr(), float(self.constraint),
                     self.xl.data_ptr(), self.logdet.data_ptr(), B, n, s)
         self.ldj.zero_()
-        for op in self.ops:
-            k = op[0]
-            if k == "coupling":
-                _, mod, x, z, sv = op
-                mod.engine().forward(x, False, self.dtype, False, saved=sv, prepare=False, ldj_sample=self.ldj,
-                                     z_out=z)
-            elif k == "squeeze":
-                _, a, b = op
-                L.squeeze(a.data_ptr(), b.data_ptr(), *a.shape, s)
-            elif k == "undo":
-                _, a, b = op
-                L.undo_squeeze(a.data_ptr(), b.data_ptr(), *b.shape, s)
-            elif k == "factor_out":
-                _, a, on, off = op
-                L.factor_out(a.data_ptr(), on.data_ptr(), off.data_ptr(), *a.shape, s)
-            else:
-                _, on, off, full = op
-                L.restore(on.data_ptr(), off.data_ptr(), full.data_ptr(), *full.shape, s)
+        self.program.forward(lambda k, st: st.eng.forward(st.x, False, self.dtype, False, saved=st.saved,
+                                                          prepare=False, ldj_sample=self.ldj, z_out=st.z))
         L.prior_logprob(self.z.data_ptr(), self.ldj.data_ptr(), self.lp.data_ptr(), B, self.z[0].numel(), s)
         self.ll_sum += (self.lp + self.logdet).mean().double()
         L.step_increment(self.counter.data_ptr(), s)
 
     def _capture(self):
         snap = (self.ll_sum.clone(), self.counter.clone())
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._batch()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self._batch()
-        torch.cuda.synchronize()
+        self.graph = capture_graph(self._batch)
         self.ll_sum.copy_(snap[0])
         self.counter.copy_(snap[1])
 

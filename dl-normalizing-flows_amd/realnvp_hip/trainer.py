@@ -48,45 +48,8 @@ import torch
 
 from . import _lib
 from .engine import _launch, stream_ptr
-
-
-def wn_table(engines, dtype, dev):
-    """One weight-norm descriptor table over the convs of several couplings
-    (rnvp_weight_norm_fwd refreshes all their packed weight images in two
-    launches: row norms, then both images on tiles).  None when there are no convs."""
-    import ctypes as C
-    from ._lib import WNDesc
-    from .engine import wn_tiles
-    descs = []
-    row0 = tile0 = 0
-    for eng in engines:
-        for d in eng.weights(dtype)["descs"]:
-            e = WNDesc()
-            C.memmove(C.addressof(e), C.addressof(d), C.sizeof(WNDesc))
-            e.row0, e.tile0 = row0, tile0
-            row0 += e.cout
-            tile0 += wn_tiles(e.cout, e.cin, e.ks)
-            descs.append(e)
-    if not descs:
-        return None
-    tab = (WNDesc * len(descs))(*descs)
-    from .engine import upload
-    t = upload(bytes(tab), dev)
-    return (t, len(descs), row0, tile0)
-
-
-def weights_key(engines, dtype):
-    """Identity of the packed-weight arenas of these couplings: changes when
-    a coupling's parameter storage moved (e.g. a FlowTrainer re-pointed the
-    parameters into its flat arena), which makes CouplingEngine.weights()
-    rebuild -- and free -- the arena a weight-norm table or a captured graph
-    points into."""
-    return tuple(e.weights(dtype)["key"] for e in engines)
-
-
-def wn_forward(table, dtype):
-    t, n, rows, tiles = table
-    _lib.lib().weight_norm_fwd(t.data_ptr(), n, rows, tiles, 1 if dtype == "bf16" else 0, stream_ptr())
+from .engine import weights_key, wn_forward, wn_table  # noqa: F401 (importable from this module too)
+from .program import FACTOR_OUT, RESTORE, SQUEEZE, UNDO, FlowProgram
 
 
 def arena_blocks(model):
@@ -458,41 +421,15 @@ class FlowTrainer:
         dev = self.dev
         f32 = dict(device=dev, dtype=torch.float32)
         self.pix = torch.zeros(B, C, S, S, **f32)
-        self.xl = torch.empty(B, C, S, S, **f32)
         self.logdet = torch.zeros(B, **f32)
         self.ldj = torch.zeros(B, **f32)
         self.prior = torch.zeros(B, dtype=torch.float64, device=dev)
         self.lp = torch.empty(B, **f32)
         self.g_lp = torch.full((B,), -1.0 / B, **f32)
         self.ll_acc = torch.zeros(1, dtype=torch.float64, device=dev)
-        self.stages = []   # forward program: ("coupling", mod, eng, in, out, sv, block) | perm ops
-        cur = self.xl
-        c, s = C, S
-        offs = []
-        for si in range(1, m.n_scales):
-            ckbd, chan = m._scale_mods(si)
-            for mod in ckbd:
-                cur = self._add_coupling(mod, cur)
-            sq = torch.empty(B, 4 * c, s // 2, s // 2, **f32)
-            self.stages.append(("squeeze", cur, sq))
-            cur = sq
-            for mod in chan:
-                cur = self._add_coupling(mod, cur)
-            un = torch.empty(B, c, s, s, **f32)
-            self.stages.append(("undo", cur, un))
-            on = torch.empty(B, 2 * c, s // 2, s // 2, **f32)
-            off = torch.empty_like(on)
-            self.stages.append(("factor_out", un, on, off))
-            offs.append(off)
-            cur = on
-            c, s = 2 * c, s // 2
-        for mod in m._scale_mods(m.n_scales)[0]:
-            cur = self._add_coupling(mod, cur)
-        for off in reversed(offs):
-            full = torch.empty(B, off.shape[1] // 2, off.shape[2] * 2, off.shape[3] * 2, **f32)
-            self.stages.append(("restore", cur, off, full))
-            cur = full
-        self.z = cur
+        # the flow program (program.py): its couplings carry their slice of the gradient arena
+        self.program = FlowProgram(m, B, dev, self.dtype, True, alloc=self._alloc_coupling)
+        self.stages, self.xl, self.z = self.program.stages, self.program.x, self.program.z
         # backward buffers: a gradient buffer per forward tensor
         self.gbuf = {}
         self._build_links(chain)
@@ -509,43 +446,42 @@ class FlowTrainer:
         e.g. without out_bn) keeps every coupling's in / out parts, the
         permutation kernels and the prior as separate launches."""
         from ._lib import LinkArgs, RNVP_LINK_FINAL, RNVP_LINK_SAME, RNVP_LINK_SQUEEZE, RNVP_LINK_UNFACTOR
-        self.cidx = [i for i, st in enumerate(self.stages) if st[0] == "coupling"]
+        self.cidx = [i for i, st in enumerate(self.stages) if st.kind == "coupling"]
         self.links = None
         if not chain:
             return
         types = []
         for k, i in enumerate(self.cidx):
             j = self.cidx[k + 1] if k + 1 < len(self.cidx) else len(self.stages)
-            between = [self.stages[m][0] for m in range(i + 1, j)]
-            a = self.stages[i][2]
+            between = [st.kind for st in self.stages[i + 1:j]]
+            a = self.stages[i].eng
             if not a.hp.coupling_bn:
                 return
             if k + 1 == len(self.cidx):
-                if any(b != "restore" for b in between):
+                if any(b != RESTORE for b in between):
                     return
                 types.append(RNVP_LINK_FINAL)
                 continue
-            n = self.stages[j][2]
+            n = self.stages[j].eng
             if between == [] and a.chains_into(n):
                 types.append(RNVP_LINK_SAME)
-            elif between == ["squeeze"] and a.kind == 0 and n.kind == 1:
+            elif between == [SQUEEZE] and a.kind == 0 and n.kind == 1:
                 types.append(RNVP_LINK_SQUEEZE)
-            elif between == ["undo", "factor_out"] and a.kind == 1 and n.kind == 0:
+            elif between == [UNDO, FACTOR_OUT] and a.kind == 1 and n.kind == 0:
                 types.append(RNVP_LINK_UNFACTOR)
             else:
                 return
         self.links = types
         self.link_fwd, self.link_bwd = [], []
         for k, (i, lt) in enumerate(zip(self.cidx, types)):
-            _, mod, eng, x, z, sv, block = self.stages[i]
             la = LinkArgs(lt, self.g_lp.data_ptr(), self.prior.data_ptr(), None, None)
-            nc = int(_lib.lib().link_nclass(lt, eng.kind))
+            nc = int(_lib.lib().link_nclass(lt, self.stages[i].eng.kind))
             if lt == RNVP_LINK_FINAL:
                 nf = nb = None
             else:
-                _, _, neng, nx, _, nsv, nblock = self.stages[self.cidx[k + 1]]
-                nf = (neng, nsv, nx)
-                nb = (neng, nsv, nx, self._g(nx), nblock)
+                n = self.stages[self.cidx[k + 1]]
+                nf = (n.eng, n.saved, n.x)
+                nb = (n.eng, n.saved, n.x, self._g(n.x), n.block)
             self.link_fwd.append(dict(nclass=nc, args=la, nxt=nf))
             self.link_bwd.append(dict(nclass=nc, args=la, nxt=nb))
 
@@ -556,7 +492,7 @@ class FlowTrainer:
         table covers the early couplings (few parameters, needed at once), the
         second the late, deep couplings (most of the parameters), which the
         side stream prepares while the early couplings run."""
-        engines = [st[2] for st in self.stages if st[0] == "coupling"]
+        engines = [st.eng for st in self.program.couplings]
         self.wn_split = min(len(engines), max(1, len(engines) * 3 // 7))
         self.wn_tables = [t for t in (wn_table(engines[:self.wn_split], self.dtype, self.dev),
                                       wn_table(engines[self.wn_split:], self.dtype, self.dev)) if t is not None]
@@ -602,15 +538,13 @@ class FlowTrainer:
             e.db_off = e.db_off + off if e.db_off >= 0 else -1
             e.blk0 += b0
             return e
-        for st in self.stages:
-            if st[0] != "coupling":
-                continue
-            eng, sv, block = st[2], st[5], st[6]
+        for st in self.program.couplings:
+            eng, sv, block = st.eng, st.saved, st.block
             off = (block.data_ptr() - base) // 4
             ws = eng.weights(self.dtype)
             if ws["blocks"] < 0:
                 self.param_pass_reason = "a conv row of %s does not fit the fused pass's LDS" % self._module_name(
-                    st[1])
+                    st.mod)
                 return
             if self.pg is None and not self.clip:
                 # single process: every coupling's pass is deferred to ONE launch
@@ -627,7 +561,7 @@ class FlowTrainer:
                 a = off + d.dv_off
                 if not (mask[a:a + d.cout * kr] == 1).all():
                     self.param_pass_reason = "a conv of %s has frozen or regularised weight_v" % self._module_name(
-                        st[1])
+                        st.mod)
                     return
                 covered[a:a + d.cout * kr] = True
                 if d.g and d.dg_off >= 0:
@@ -715,7 +649,7 @@ class FlowTrainer:
         self.adam_ranges = None
         if self.pg is not None or not self.overlap or self.fused or self.links is not None or self.clip:
             return
-        blocks = [st[6] for st in self.stages if st[0] == "coupling"]
+        blocks = [st.block for st in self.program.couplings]
         base = self.grad.data_ptr()
         offs = [(b.data_ptr() - base) // 4 for b in blocks]
         if offs != sorted(offs) or offs[0] != 0:
@@ -728,7 +662,7 @@ class FlowTrainer:
         """All-reduce buckets in backward order (dist.bucket_schedule over the
         couplings' gradient blocks); bucket k is issued right after coupling
         bucket_after[k]'s backward has been scheduled."""
-        blocks = [st[6] for st in self.stages if st[0] == "coupling"]
+        blocks = [st.block for st in self.program.couplings]
         base = self.grad.data_ptr()
         spans = [((b.data_ptr() - base) // 4, b.numel()) for b in blocks]
         if spans != arena_blocks(self.model):
@@ -777,16 +711,13 @@ class FlowTrainer:
         g._get_backend(self.dev).eager_connect_single_device(self.dev)
         return g
 
-    def _add_coupling(self, mod, x):
+    def _alloc_coupling(self, mod, x):
         eng = mod.engine()
         B, C, H, W = x.shape
         sv = eng.alloc_saved(B, H, W, self.dtype, self.dev, True)
-        z = torch.empty_like(x)
         first = next(n for n, _ in mod.named_parameters())
         name = self._module_name(mod) + "." + first
-        block = self.grad[self.offsets[name]:self.offsets[name] + eng.n_params]
-        self.stages.append(("coupling", mod, eng, x, z, sv, block))
-        return z
+        return eng, sv, self.grad[self.offsets[name]:self.offsets[name] + eng.n_params]
 
     def _module_name(self, mod):
         if not hasattr(self, "_names"):
@@ -835,27 +766,13 @@ class FlowTrainer:
                         self.logdet.data_ptr(), B, n, s)
         self.ldj.zero_()
         late_ready = self._wn_prepare()
-        ci = 0
-        for i, st in enumerate(self.stages):
-            if st[0] == "coupling":
-                if ci == self.wn_split and late_ready is not None:
-                    torch.cuda.current_stream().wait_event(late_ready)
-                ci += 1
-                _, mod, eng, x, z, sv, _ = st
-                eng.forward(x, True, self.dtype, False, saved=sv, prepare=False, ldj_sample=self.ldj, z_out=z,
-                            zero_sums=False)
-            elif st[0] == "squeeze":
-                _, a, b = st
-                L.squeeze(a.data_ptr(), b.data_ptr(), *a.shape, s)
-            elif st[0] == "undo":
-                _, a, b = st
-                L.undo_squeeze(a.data_ptr(), b.data_ptr(), *b.shape, s)
-            elif st[0] == "factor_out":
-                _, a, on, off = st
-                L.factor_out(a.data_ptr(), on.data_ptr(), off.data_ptr(), *a.shape, s)
-            else:
-                _, on, off, full = st
-                L.restore(on.data_ptr(), off.data_ptr(), full.data_ptr(), *full.shape, s)
+
+        def coupling(ci, st):
+            if ci == self.wn_split and late_ready is not None:
+                torch.cuda.current_stream().wait_event(late_ready)
+            st.eng.forward(st.x, True, self.dtype, False, saved=st.saved, prepare=False, ldj_sample=self.ldj,
+                           z_out=st.z, zero_sums=False)
+        self.program.forward(coupling)
         L.prior_logprob(self.z.data_ptr(), self.ldj.data_ptr(), self.lp.data_ptr(), B, self.z[0].numel(), s)
         self.ll_acc += (self.lp + self.logdet).mean().double()
 
@@ -869,8 +786,9 @@ class FlowTrainer:
         L = _lib.lib()
         s = stream_ptr()
         B = self.B
-        _, _, eng0, x0, _, sv0, _ = self.stages[self.cidx[0]]
-        a0 = eng0.link_args(sv0, x0)
+        first = self.program.couplings[0]
+        x0 = first.x
+        a0 = first.eng.link_args(first.saved, x0)
         n_el, esz = x0.numel(), 2 if self.dtype == "bf16" else 4
         cs_h0 = a0.cs_h0
         if not self.external_input:
@@ -880,11 +798,10 @@ class FlowTrainer:
         else:
             _launch("coupling", 8 * n_el + esz * x0[:, 0].numel() * cs_h0, 0.0, L.coupling_in_fwd, C.byref(a0), s)
         late_ready = self._wn_prepare()
-        for k, i in enumerate(self.cidx):
+        for k, st in enumerate(self.program.couplings):
             if k == self.wn_split and late_ready is not None:
                 torch.cuda.current_stream().wait_event(late_ready)
-            _, mod, eng, x, z, sv, _ = self.stages[i]
-            eng.forward_link(x, sv, self.ldj, self.link_fwd[k])
+            st.eng.forward_link(st.x, st.saved, self.ldj, self.link_fwd[k])
         L.flow_lp_finish(self.prior.data_ptr(), self.ldj.data_ptr(), self.logdet.data_ptr(),
                          0 if self.external_input else 1, self.lp.data_ptr(), self.ll_acc.data_ptr(), B, s)
 
@@ -917,33 +834,18 @@ class FlowTrainer:
         gz = self._g(self.z)
         L.prior_logprob_bwd(self.z.data_ptr(), self.g_lp.data_ptr(), gz.data_ptr(), B, self.z[0].numel(), s)
         n_coupling = len(self.cidx)
-        ci = n_coupling
-        for i in reversed(range(len(self.stages))):
-            st = self.stages[i]
-            if st[0] == "coupling":
-                ci -= 1
-                _, mod, eng, x, z, sv, block = st
-                after = None
-                if self.adam_ranges is not None:
-                    lo, hi = self.adam_ranges[ci]
-                    after = (lambda lo=lo, hi=hi: self._adam_range(lo, hi))
-                opt = "defer" if self._slab_table is not None else None
-                eng.backward(sv, self._g(z), None, self.g_lp, block, gx=self._g(x), side=self.side, after=after,
-                             zero_at_end=True, opt=opt, multi=self._multi_list(opt))
-                self._issue_buckets(ci, n_coupling)
-            elif st[0] == "squeeze":
-                _, a, b = st
-                L.undo_squeeze(self._g(b).data_ptr(), self._g(a).data_ptr(), *a.shape, s)
-            elif st[0] == "undo":
-                _, a, b = st
-                L.squeeze(self._g(b).data_ptr(), self._g(a).data_ptr(), *b.shape, s)
-            elif st[0] == "factor_out":
-                _, a, on, off = st
-                L.restore(self._g(on).data_ptr(), self._g(off).data_ptr(), self._g(a).data_ptr(), *a.shape, s)
-            else:
-                _, on, off, full = st
-                L.factor_out(self._g(full).data_ptr(), self._g(on).data_ptr(), self._g(off).data_ptr(),
-                             *full.shape, s)
+
+        def coupling(ci, st):
+            after = None
+            if self.adam_ranges is not None:
+                lo, hi = self.adam_ranges[ci]
+                after = (lambda lo=lo, hi=hi: self._adam_range(lo, hi))
+            opt = "defer" if self._slab_table is not None else None
+            st.eng.backward(st.saved, self._g(st.z), None, self.g_lp, st.block, gx=self._g(st.x), side=self.side,
+                            after=after, zero_at_end=True, opt=opt, multi=self._multi_list(opt))
+            self._issue_buckets(ci, n_coupling)
+        # the permutations' gradients: the inverse program over the gradient buffers
+        self.program.inverse(coupling, buf=self._g)
 
     def _backward_links(self):
         """Backward over the coupling links, last coupling first: its link
@@ -957,10 +859,10 @@ class FlowTrainer:
         opt = "defer" if self._slab_table is not None else None
         pending, pending_ci = [], None
         for k in reversed(range(n_coupling)):
-            _, mod, eng, x, z, sv, block = self.stages[self.cidx[k]]
+            st = self.program.couplings[k]
             mine = []
-            eng.backward_link(sv, self.link_bwd[k], block, self._g(x), self.g_lp, k == 0, mine, opt=opt,
-                              multi=self._multi_list(opt))
+            st.eng.backward_link(st.saved, self.link_bwd[k], st.block, self._g(st.x), self.g_lp, k == 0, mine,
+                                 opt=opt, multi=self._multi_list(opt))
             self._run_pending(pending, pending_ci, n_coupling)
             pending, pending_ci = mine, k
         self._run_pending(pending, pending_ci, n_coupling)
