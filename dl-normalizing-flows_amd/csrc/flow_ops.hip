@@ -1,10 +1,10 @@
-// Flow-level kernels: index maps, logit transform, prior log-prob, regulariser,
-// BN running stats, fused Adam.  All HBM-bound elementwise / reduction work.
+// Flow-level kernels: index maps, logit transform, scoring, prior log-prob,
+// regulariser, BN running stats, fused Adam.  All HBM-bound elementwise / reduction work.
 #include <math.h>
 
 #include "coupling_common.h"
 
-extern "C" int rnvp_version(void) { return 112; }
+extern "C" int rnvp_version(void) { return 113; }
 
 extern "C" int rnvp_struct_size(int which) {
     switch (which) {
@@ -184,22 +184,32 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t ctr) {
 
 __device__ __forceinline__ float softplusf(float v) { return v > 20.f ? v : log1pf(expf(v)); }
 
+// one element of the transform (utils.py:45-66): the dequantised, constrained
+// pixel's logit, and its term of the log-determinant (sp_pre = softplus(-logit(cst)))
+__device__ __forceinline__ float logit_elem(float x, float u, float cst) {
+    float v = (x * 255.f + u) / 256.f;
+    v = ((v * 2.f - 1.f) * cst + 1.f) / 2.f;
+    return logf(v) - logf(1.f - v);
+}
+__device__ __forceinline__ float logit_ld(float l, float sp_pre) { return softplusf(l) + softplusf(-l) - sp_pre; }
+__device__ __forceinline__ float logit_sp_pre(float cst) {
+    return softplusf(-(float)(log((double)cst) - log(1.0 - (double)cst)));
+}
+
 __global__ void k_logit_fwd(const float* __restrict__ x, const float* __restrict__ noise, uint64_t seed, uint64_t offset,
                             const long long* epoch, float cst, float* __restrict__ y, float* __restrict__ logdet, int n) {
     __shared__ double red[16];
     const int b = blockIdx.x;
     const long long base = (long long)b * n;
     if (epoch) offset += (uint64_t)epoch[0] * (uint64_t)gridDim.x * (uint64_t)n;
-    const float sp_pre = softplusf(-(float)(log((double)cst) - log(1.0 - (double)cst)));
+    const float sp_pre = logit_sp_pre(cst);
     double acc = 0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         long long e = base + i;
         float u = noise ? noise[e] : philox_uniform(seed, offset + (uint64_t)e);
-        float v = (x[e] * 255.f + u) / 256.f;
-        v = ((v * 2.f - 1.f) * cst + 1.f) / 2.f;
-        float l = logf(v) - logf(1.f - v);
+        float l = logit_elem(x[e], u, cst);
         y[e] = l;
-        acc += (double)(softplusf(l) + softplusf(-l) - sp_pre);
+        acc += (double)logit_ld(l, sp_pre);
     }
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) logdet[b] = (float)acc;
@@ -239,7 +249,7 @@ __global__ __launch_bounds__(256) void k_flow_in(const float* __restrict__ x, ui
         lds_zero(red, 2 * Cb);
         __syncthreads();
     }
-    const float sp_pre = softplusf(-(float)(log((double)cst) - log(1.0 - (double)cst)));
+    const float sp_pre = logit_sp_pre(cst);
     const int total = C * tp;
     double acc = 0.0;
     for (int e0 = 0; e0 < total; e0 += 256) {   // block-uniform: the segment sums need every lane
@@ -250,11 +260,9 @@ __global__ __launch_bounds__(256) void k_flow_in(const float* __restrict__ x, ui
         float l = 0.f;
         if (ok) {
             const float u = philox_uniform(seed, offset + (uint64_t)idx);
-            float v = (x[idx] * 255.f + u) / 256.f;
-            v = ((v * 2.f - 1.f) * cst + 1.f) / 2.f;
-            l = logf(v) - logf(1.f - v);
+            l = logit_elem(x[idx], u, cst);
             y[idx] = l;
-            acc += (double)(softplusf(l) + softplusf(-l) - sp_pre);
+            acc += (double)logit_ld(l, sp_pre);
         }
         if (first) {
             int cb = c;
@@ -299,6 +307,158 @@ extern "C" int rnvp_flow_in_fwd(const float* x, uint64_t seed, const long long* 
     k_flow_in<<<grid, 256, 16 * (size_t)Cb, (hipStream_t)stream>>>(x, seed, epoch, (uint64_t)B * C * HW, constraint,
                                                                    y, logdet, first ? *first : none, first ? 1 : 0, C,
                                                                    HW, TP, seg);
+    RNVP_LAUNCH_CHECK();
+    return RNVP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// scoring (include/realnvp_hip.h, "scoring"): per-image log-likelihoods of
+// ragged batches, K noise draws per image, one device-resident control block
+//   k_score_in       the logit transform with per-IMAGE noise, a chunk of one
+//                    sample per workgroup
+//   k_score_rows     one workgroup per row: this draw's log-likelihood, the
+//                    online log-sum-exp over the draws, the finalised score
+//   k_score_advance  one workgroup, behind the rows: the block's counters
+// ---------------------------------------------------------------------------
+constexpr int SCORE_CHUNKS = 8;   // per sample: one fp32 atomic on logdet[b] each (header: the rounding bound)
+
+__global__ __launch_bounds__(256) void k_score_in(const float* __restrict__ x, const float* __restrict__ noise,
+                                                  uint64_t seed, const rnvp_score_ctl* __restrict__ ctl, float cst,
+                                                  float* __restrict__ y, float* __restrict__ logdet, int n, int chunks,
+                                                  int chunk) {
+    __shared__ double red[16];
+    const int b = blockIdx.x / chunks, i0 = (blockIdx.x - b * chunks) * chunk, i1 = min(n, i0 + chunk);
+    // the image's own stream: counter ((first + b) K + draw) n + e
+    const uint64_t ctr = ((uint64_t)(ctl->first + b) * (uint64_t)ctl->n_draws + (uint64_t)ctl->draw) * (uint64_t)n;
+    const long long base = (long long)b * n;
+    const float sp_pre = logit_sp_pre(cst);
+    double acc = 0.0;
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+        const float u = noise ? noise[base + i] : philox_uniform(seed, ctr + (uint64_t)i);
+        const float l = logit_elem(x[base + i], u, cst);
+        y[base + i] = l;
+        acc += (double)logit_ld(l, sp_pre);
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0 && i0 < i1) atomicAdd(&logdet[b], (float)acc);
+}
+
+extern "C" int rnvp_score_in_fwd(const float* x, const float* noise, uint64_t seed, const rnvp_score_ctl* ctl,
+                                 float constraint, float* y, float* logdet, int B, int C, int H, int W, void* stream) {
+    if (!x || !y || !logdet || !ctl || B < 0 || C <= 0 || H <= 0 || W <= 0) return RNVP_E_INVALID;
+    if (((((uintptr_t)x) | ((uintptr_t)noise) | ((uintptr_t)y) | ((uintptr_t)logdet)) & 3) || (((uintptr_t)ctl) & 7))
+        return RNVP_E_INVALID;
+    const long long n = (long long)C * H * W;
+    if (n > 0x7fffffffLL) return RNVP_E_INVALID;
+    if (B == 0) return RNVP_OK;
+    // more workgroups than samples at small B, a chunk no shorter than the workgroup's 256 threads
+    int chunks = 1;
+    while (chunks < SCORE_CHUNKS && (long long)B * chunks < 1024 && n / (2 * chunks) >= 256) chunks *= 2;
+    if ((long long)B * chunks > 0x7fffffffLL) return RNVP_E_INVALID;
+    const int chunk = (int)((n + chunks - 1) / chunks);
+    k_score_in<<<B * chunks, 256, 0, (hipStream_t)stream>>>(x, noise, seed, ctl, constraint, y, logdet, (int)n, chunks,
+                                                             chunk);
+    RNVP_LAUNCH_CHECK();
+    return RNVP_OK;
+}
+
+__global__ __launch_bounds__(512) void k_score_rows(const float* __restrict__ z, float* __restrict__ ldj,
+                                                    float* __restrict__ logdet, float* __restrict__ run,
+                                                    float* __restrict__ lp, const rnvp_score_ctl* __restrict__ ctl,
+                                                    int n) {
+    __shared__ double red[16];
+    const int b = blockIdx.x;
+    const float* zb = z + (long long)b * n;
+    const double c = 0.91893853320467274178;   // log(2 pi) / 2
+    double acc = 0.0;
+    if ((n & 3) == 0 && (((uintptr_t)z) & 15) == 0) {
+        for (int i = threadIdx.x; i < (n >> 2); i += blockDim.x) {
+            const floatx4 v = ((const floatx4*)zb)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc += -0.5 * (double)v[j] * (double)v[j] - c;
+        }
+    } else {
+        for (int i = threadIdx.x; i < n; i += blockDim.x) acc += -0.5 * (double)zb[i] * (double)zb[i] - c;
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x != 0) return;
+    const double ll = acc + (double)ldj[b] + (double)logdet[b];
+    ldj[b] = 0.f;
+    logdet[b] = 0.f;
+    if (b >= ctl->n_valid) return;   // a padding row: nothing but the zeroing
+    if (lp) lp[b] = (float)ll;
+    // online log-sum-exp over the draws: m is an fp32 value, the exponents are
+    // taken against exactly that value, so its rounding costs nothing
+    const int K = ctl->n_draws, k = ctl->draw;
+    float m = (float)ll;
+    double s = exp(ll - (double)m);
+    if (k > 0) {
+        const float m0 = run[2 * b];
+        const double s0 = (double)run[2 * b + 1];
+        if (m0 >= m) {
+            s = s0 + exp(ll - (double)m0);
+            m = m0;
+        } else {
+            s += s0 * exp((double)m0 - (double)m);
+        }
+    }
+    if (k < K - 1) {
+        run[2 * b] = m;
+        run[2 * b + 1] = (float)s;
+        return;
+    }
+    const float score = K == 1 ? (float)ll : (float)((double)m + log(s) - log((double)K));
+    run[2 * b] = score;   // for k_score_advance's sum
+    const long long at = ctl->first + b;
+    if (at >= 0 && at < ctl->cap) ctl->scores[at] = score;
+}
+
+__global__ __launch_bounds__(256) void k_score_advance(const float* __restrict__ run, rnvp_score_ctl* ctl, int B) {
+    __shared__ float sc[256];
+    __shared__ int cfg[3];
+    // one thread reads the fields that thread 0 writes below, for all (a wave
+    // that started late must not see the advanced draw)
+    if (threadIdx.x == 0) {
+        cfg[0] = ctl->n_draws;
+        cfg[1] = ctl->draw;
+        cfg[2] = max(0, min(ctl->n_valid, B));
+    }
+    __syncthreads();
+    const int K = cfg[0], k = cfg[1], nv = cfg[2];
+    if (k < K - 1) {
+        if (threadIdx.x == 0) ctl->draw = k + 1;
+        return;
+    }
+    // the finalised scores, added in row order by one thread (256 rows' loads at a time)
+    double sum = ctl->ll_sum;
+    for (int b0 = 0; b0 < nv; b0 += 256) {
+        if (b0 + (int)threadIdx.x < nv) sc[threadIdx.x] = run[2 * (b0 + (int)threadIdx.x)];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int j = 0; j < min(256, nv - b0); ++j) sum += (double)sc[j];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ctl->ll_sum = sum;
+        if (ctl->first + nv > ctl->cap) ctl->overflow = 1;
+        ctl->n_scored = ctl->n_scored + nv;
+        ctl->first = ctl->first + nv;
+        ctl->draw = 0;
+    }
+}
+
+extern "C" int rnvp_score_struct_size(void) { return (int)sizeof(rnvp_score_ctl); }
+
+extern "C" int rnvp_score_finish(const float* z, float* ldj, float* logdet, float* run, float* lp, rnvp_score_ctl* ctl,
+                                 int B, int n_per_sample, void* stream) {
+    if (!z || !ldj || !logdet || !run || !ctl || B < 0 || n_per_sample <= 0) return RNVP_E_INVALID;
+    if (((((uintptr_t)z) | ((uintptr_t)ldj) | ((uintptr_t)logdet) | ((uintptr_t)run) | ((uintptr_t)lp)) & 3) ||
+        (((uintptr_t)ctl) & 7))
+        return RNVP_E_INVALID;
+    if (B == 0) return RNVP_OK;
+    k_score_rows<<<B, 512, 0, (hipStream_t)stream>>>(z, ldj, logdet, run, lp, ctl, n_per_sample);
+    RNVP_LAUNCH_CHECK();
+    k_score_advance<<<1, 256, 0, (hipStream_t)stream>>>(run, ctl, B);
     RNVP_LAUNCH_CHECK();
     return RNVP_OK;
 }

@@ -9,6 +9,8 @@ Layout:
   trainer.py     fused NLL training step (flat parameter arena, fused Adam,
                  HIP-graph capture, RCCL data parallelism)
   optim.py       FusedAdam: torch.optim.Adam drop-in for the reference loop
+  scorer.py      FlowScorer: per-image log-likelihoods (ragged batches, K-draw bound)
 """
 from ._lib import LIB_PATH, lib  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
+from .scorer import FlowScorer  # noqa: F401

@@ -106,6 +106,11 @@ class EmaCtl(C.Structure):
     _fields_ = [("decay", f32), ("warmup", i32), ("applied", f32), ("pad", i32), ("n_updates", i64)]
 
 
+class ScoreCtl(C.Structure):
+    _fields_ = [("scores", vp), ("cap", i64), ("first", i64), ("n_scored", i64), ("ll_sum", f64),
+                ("n_valid", i32), ("n_draws", i32), ("draw", i32), ("overflow", i32)]
+
+
 WGRAD_GROUP_MAX = 24
 
 
@@ -234,6 +239,9 @@ _SIGS = {
     "rnvp_ema_struct_size": (i32, []),
     "rnvp_ema_update": (i32, [vp, vp, i64, vp, vp, i64, vp, vp]),
     "rnvp_ema_swap": (i32, [vp, vp, i64, vp]),
+    "rnvp_score_struct_size": (i32, []),
+    "rnvp_score_in_fwd": (i32, [vp, vp, C.c_uint64, vp, f32, vp, vp, i32, i32, i32, i32, vp]),
+    "rnvp_score_finish": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "rnvp_fill_f64": (i32, [vp, i64, f64, vp]),
     "rnvp_net_group_prepare": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "rnvp_net_group": (i32, [vp, i32, i32, i32, i32, i32, vp]),
@@ -253,7 +261,7 @@ class _Lib:
             fn.argtypes = args
             raw = name in ("rnvp_version", "rnvp_struct_size", "rnvp_stat_shards", "rnvp_wgrad_slabs", "rnvp_wgrad_replicas",
                            "rnvp_link_nclass", "rnvp_conv2d_check", "rnvp_conv2d_family", "rnvp_wgrad_class", "rnvp_wgrad_multi_plan", "rnvp_wgrad_multi_struct_size",
-                           "rnvp_grad_sumsq_parts", "rnvp_ema_struct_size",
+                           "rnvp_grad_sumsq_parts", "rnvp_ema_struct_size", "rnvp_score_struct_size",
                            "rnvp_weight_norm_tiles", "rnvp_weight_norm_opt_blocks",
                            "rnvp_net_group_prepare") or res is not i32
             setattr(self, name[len("rnvp_"):], fn if raw else self._wrap(name, fn))
@@ -269,9 +277,10 @@ class _Lib:
             if self.dll.rnvp_wgrad_multi_struct_size(i) != C.sizeof(m):
                 raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"
                                    % (path, m.__name__, self.dll.rnvp_wgrad_multi_struct_size(i), C.sizeof(m)))
-        if self.dll.rnvp_ema_struct_size() != C.sizeof(EmaCtl):
-            raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"
-                               % (path, EmaCtl.__name__, self.dll.rnvp_ema_struct_size(), C.sizeof(EmaCtl)))
+        for m, size in ((EmaCtl, self.dll.rnvp_ema_struct_size()), (ScoreCtl, self.dll.rnvp_score_struct_size())):
+            if size != C.sizeof(m):
+                raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"
+                                   % (path, m.__name__, size, C.sizeof(m)))
 
     def _wrap(self, name, fn):
         dll = self.dll

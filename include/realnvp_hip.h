@@ -708,6 +708,69 @@ int rnvp_ema_update(float* ema, const float* param, long long n, rnvp_ema_ctl* e
                     long long step_add, const rnvp_step_ctl* ctl /* may be NULL */, void* stream);
 int rnvp_ema_swap(float* a, float* b, long long n, void* stream);
 
+/* ---- scoring ---------------------------------------------------------------
+ * Per-image log-likelihoods of a dataset (nats; the validation loop of
+ * train.py:214-233 without its mean): batches of up to B images, the last one
+ * ragged, and the K-draw importance bound log(1/K sum_k p(x + u_k)) over K
+ * draws of the uniform dequantisation noise.  One draw of one batch is
+ *   rnvp_score_in_fwd -> the eval-mode flow forward (per-sample ldj) -> rnvp_score_finish
+ * and a device-resident control block carries everything that changes from one
+ * replay to the next, so one captured graph serves a whole pass: the host
+ * writes its fields with stream-ordered copies / fills, rnvp_score_finish
+ * advances it, and the library never reads it on the host.
+ *
+ * rnvp_score_in_fwd is rnvp_logit_fwd's transform (logdet[b] += as
+ * rnvp_flow_in_fwd: the caller zeroes logdet once, rnvp_score_finish leaves it
+ * zero) over chunks of every sample, with noise that belongs to the IMAGE, not
+ * to its slot in the batch: with n = C*H*W, element e of row b in draw
+ * k = ctl->draw takes the Philox uniform of counter
+ *   ((ctl->first + b) * n_draws + k) * n + e
+ * so an image's score does not depend on the batch size or on its neighbours.
+ * A non-NULL noise ([B][n]) replaces the Philox values of this draw.  Reads
+ * ctl, never writes it.  Rows >= n_valid are transformed like any other (their
+ * pixels are the caller's; zeros keep every value finite).  A sample is cut
+ * into at most 8 chunks, one fp32 atomic each: logdet[b] stays within 10
+ * roundings (6e-7 relative; its terms are all positive) of the exact sum.
+ *
+ * rnvp_score_finish, a row kernel and then a one-workgroup advance:
+ *   ll[b] = sum_i (-z_i^2/2 - log(2 pi)/2) + ldj[b] + logdet[b]   in fp64,
+ *   stored to lp[b] when lp != NULL (b < n_valid); ldj[b] = logdet[b] = 0
+ *   afterwards.
+ *   run ([B][2] fp32: running max m, sum s of exp(ll - m)) is reset in draw 0
+ *   and updated online; in draw K-1 row b < n_valid is finalised:
+ *     score = m + log(s) - log(K)      (ll itself for K == 1)
+ *   stored to scores[first + b] when first + b < cap (and left in run[b][0]).
+ *   Rows >= n_valid write nothing but the zeroing.
+ *   The advance (its own launch behind the rows, which all read the block):
+ *   draw = (draw + 1) % K; after the last draw ll_sum += the finalised scores,
+ *   one fp64 addition per row in row order (no atomics: two passes over the
+ *   same scores give the same bits), n_scored += n_valid, first += n_valid,
+ *   and overflow = 1 when first + n_valid > cap (nothing is written past cap,
+ *   no error status: the host reads the flag with the results).
+ *
+ * Both check their arguments before any HIP call: RNVP_E_INVALID for a NULL
+ * x / y / logdet / ctl (z / ldj / logdet / run / ctl), a pointer that is not
+ * 4-byte (ctl: 8-byte) aligned, B < 0, C / H / W <= 0 or C*H*W > 2^31 - 1
+ * (n_per_sample <= 0).  B == 0 is RNVP_OK with nothing launched.  1 <=
+ * n_valid <= B and n_draws >= 1 are the writer's responsibility. */
+typedef struct rnvp_score_ctl {
+    float* scores;          /* host: destination of the pass, cap floats (device memory) */
+    long long cap;          /* host */
+    long long first;        /* global index of row 0 of the running batch; device-advanced */
+    long long n_scored;     /* images finalised in this pass; device */
+    double ll_sum;          /* sum of their scores, fp64, added in row order; device */
+    int n_valid;            /* host: rows of the running batch that are images, 1..B */
+    int n_draws;            /* host: K >= 1 */
+    int draw;               /* 0..K-1; device-advanced */
+    int overflow;           /* device: set when first + n_valid > cap */
+} rnvp_score_ctl;
+/* sizeof(rnvp_score_ctl), for a binding's mirror (the list of rnvp_struct_size is closed) */
+int rnvp_score_struct_size(void);
+int rnvp_score_in_fwd(const float* x, const float* noise /* may be NULL */, uint64_t seed, const rnvp_score_ctl* ctl,
+                      float constraint, float* y, float* logdet, int B, int C, int H, int W, void* stream);
+int rnvp_score_finish(const float* z, float* ldj, float* logdet, float* run, float* lp /* may be NULL */,
+                      rnvp_score_ctl* ctl, int B, int n_per_sample, void* stream);
+
 /* ---- net steps ------------------------------------------------------------
  * One s/t-net step as a table entry (rnvp_net_group): a conv (rnvp_conv2d
  * semantics) or a BatchNorm-backward apply (rnvp_bn_bwd_apply semantics).
