@@ -149,15 +149,17 @@ __device__ __forceinline__ double wave_sum(double v) {
 // Sum over the 16 lanes of a DPP row (lanes 16r .. 16r+15 = one MFMA column
 // group); every lane of the row gets the result.  row_ror butterfly on the
 // VALU (no LDS round trip: __shfl_xor lowers to ds_bpermute).
+// (every lane of a row_ror / quad_perm has a source lane: bound_ctrl leaves the
+// move no `old` operand to zero first)
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, true);
     return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
 }
 __device__ __forceinline__ float row_sum16(float v) {
@@ -167,6 +169,103 @@ __device__ __forceinline__ float row_sum16(float v) {
 __device__ __forceinline__ double row_sum16(double v) {
     v += dpp_d<0x128>(v); v += dpp_d<0x124>(v); v += dpp_d<0x122>(v); v += dpp_d<0x121>(v);
     return v;
+}
+
+// ---- transposing row reduction ---------------------------------------------
+// Several values per lane summed over the 16 lanes of a DPP row as a
+// reduce-scatter: at lane distance 8, 4, 2, 1 a lane keeps one half of its
+// values, adds its partner's copies of them and hands the other half over,
+// until one value is left (15 adds for 16 values; row_sum16 on each spends
+// 64).  The pairs are row_sum16's -- lane i with i ^ 8, then (i, i ^ 8) with
+// (i ^ 4, i ^ 12), then the lanes that differ in bit 1, then bit 0 -- and IEEE
+// addition commutes, so every total is bitwise what row_sum16 leaves in lane 0
+// (tools/probe/row_reduce_check.hip).
+//
+// dpp_into: the lanes of the 4-lane banks in BANK (lanes 4b .. 4b+3 are bank b)
+// take v from their CTRL source lane, the others keep `old`: the move is the
+// select.
+template <int CTRL, int BANK>
+__device__ __forceinline__ float dpp_into(float old, float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, 0xf, BANK, false));
+}
+template <int CTRL, int BANK>
+__device__ __forceinline__ double dpp_into(double old, double v) {
+    const unsigned long long o = (unsigned long long)__double_as_longlong(old);
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)u, CTRL, 0xf, BANK, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(u >> 32), CTRL, 0xf, BANK, false);
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+// One distance D (4, 2 or 1) of the reduction on v[0 .. n): n >= 2 halves the
+// array (a lane whose index has bit D clear keeps v[k], one with it set keeps
+// v[k + n/2], k < n/2, in v[k]); n == 1 (distance 1 only: the two lanes of a
+// pair hold the same slot) is the plain butterfly.  Distance 4 is row_shl:4 /
+// row_shr:4, each written into the lanes of one side by bank mask; distances 2
+// and 1 are the quad_perm swaps, with the halves chosen by select.
+template <int D, int n>
+__device__ __forceinline__ void row_reduce_step(double* v, int li) {
+    static_assert(D == 4 || D == 2 || D == 1, "distance 8 is row_stats16's first step");
+    if constexpr (n >= 2) {
+        constexpr int h = n / 2;
+#pragma unroll
+        for (int k = 0; k < h; ++k) {
+            const double lo = v[k], hi = v[k + h];
+            if constexpr (D == 4) {
+                v[k] = dpp_into<0x104, 0x5>(hi, lo) + dpp_into<0x114, 0xa>(lo, hi);
+            } else {
+                const bool up = (li & D) != 0;
+                const double send = up ? lo : hi, keep = up ? hi : lo;
+                v[k] = keep + (D == 2 ? dpp_d<0x4e>(send) : dpp_d<0xb1>(send));
+            }
+        }
+    } else {
+        static_assert(n >= 2 || D == 1, "one value left before distance 1");
+        v[0] += dpp_d<0xb1>(v[0]);
+    }
+}
+
+// The conv epilogues' statistics tail: a thread's partial sums s1[J][4] /
+// s2[J][4] (J column groups of 4 channels; 8, 16 or 32 values a round) reduced
+// over the row together, and park(j, r, which, total) called in the ONE lane
+// that ends up owning column (j, r)'s sum (which = 0) or sum of squares
+// (which = 1) -- where lane 0 used to park all 8 J of them.  Input order
+// (j * 4 + r) * 2 + which.  Distance 8 (row_ror:8, by bank mask) moves the
+// partials as they are -- fp32 ones one move each -- and widens them on
+// arrival: (double)a + (double)b either way.  Every lane of the row must be
+// active.
+template <int J0, int J, typename F, typename Park>
+__device__ __forceinline__ void row_stats16_from(const F (&s1)[J][4], const F (&s2)[J][4], int li, Park&& park) {
+    constexpr int REM = J - J0;
+    constexpr int P = REM >= 4 ? 4 : (REM >= 2 ? 2 : 1);   // column groups in this round
+    constexpr int N = 8 * P, H = N / 2;
+    F w[N];
+#pragma unroll
+    for (int j = 0; j < P; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            w[(j * 4 + r) * 2] = s1[J0 + j][r];
+            w[(j * 4 + r) * 2 + 1] = s2[J0 + j][r];
+        }
+    double v[H];
+#pragma unroll
+    for (int k = 0; k < H; ++k)
+        v[k] = (double)dpp_into<0x128, 0x3>(w[k + H], w[k]) + (double)dpp_into<0x128, 0xc>(w[k], w[k + H]);
+    row_reduce_step<4, H>(v, li);
+    row_reduce_step<2, H / 2>(v, li);
+    row_reduce_step<1, (H >= 8 ? H / 4 : 1)>(v, li);
+    if constexpr (N == 32) {          // lane li: both sums of column li
+        park(J0 + (li >> 2), li & 3, 0, v[0]);
+        park(J0 + (li >> 2), li & 3, 1, v[1]);
+    } else if constexpr (N == 16) {   // lane li: column li / 2, sum li & 1
+        park(J0 + (li >> 3), (li >> 1) & 3, li & 1, v[0]);
+    } else {                          // lanes 2i, 2i + 1: column i / 2, sum i & 1
+        if (!(li & 1)) park(J0, li >> 2, (li >> 1) & 1, v[0]);
+    }
+    if constexpr (J0 + P < J) row_stats16_from<J0 + P>(s1, s2, li, park);
+}
+template <int J, typename F, typename Park>
+__device__ __forceinline__ void row_stats16(const F (&s1)[J][4], const F (&s2)[J][4], int li, Park&& park) {
+    row_stats16_from<0>(s1, s2, li, park);
 }
 
 // block-wide sum (blockDim.x multiple of 64, <= 1024); every thread gets the result

@@ -233,17 +233,10 @@ __global__ __launch_bounds__(256 * NH) void k_conv_band(rnvp_conv_args a, int sh
     }
     const bool want_sums = a.out_sums || (epi_bn && a.epi_sums);
     if (want_sums) {
-#pragma unroll
-        for (int j = 0; j < NTW; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double u1 = row_sum16(s1[j][r]), u2 = row_sum16(s2[j][r]);
-                const int col = (hf * NTW + j) * 16 + 4 * g + r;
-                if (li == 0) {
-                    red[(wid * NC + col) * 2] = u1;
-                    red[(wid * NC + col) * 2 + 1] = u2;
-                }
-            }
+        row_stats16(s1, s2, li, [&](int j, int r, int which, double u) {
+            const int col = (hf * NTW + j) * 16 + 4 * g + r;
+            red[(wid * NC + col) * 2 + which] = u;
+        });
         __syncthreads();
         double* sums = shard_ptr(epi_bn ? a.epi_sums : a.out_sums, shards, N);
         for (int n = tid; n < N; n += NTH) {

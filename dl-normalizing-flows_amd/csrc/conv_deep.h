@@ -36,6 +36,26 @@ size_t deep_lds_bytes(int cs, int W, int ks, bool bp = false) {
     return head + zrow + (act > red ? act : red);
 }
 
+// Whether an instantiation's statistics tail is the transposing row
+// reduction (row_stats16, common.h).  Not where the compiled kernel then spills
+// more registers or holds one wave per SIMD less (profiles/stat_tail_isa.txt):
+// those keep row_sum16.  The list is one compiler's register allocation: after
+// a change to deep_tile or a new hipcc, build the library with and without
+// the change and compare the two object directories,
+//   python tools/isa_budget.py <build dir before> <build dir after>
+// (every kernel's VGPRs, spills and waves per SIMD; it exits non-zero where a
+// kernel spills more VGPRs or loses a wave), and move instantiations in or out.
+template <typename T, int BN, int KSZ, bool PRO, int NW, int WK, int NC, bool FM, int BM, bool BP>
+constexpr bool deep_stats_transposed() {
+    constexpr bool F32 = sizeof(T) == 4;
+    if (NW == 8 && BN == 64) return false;                                   // the 64-channel 8-wave tiles (at the 256 cap)
+    if (NW == 4 && WK == 4 && BN == 64 && KSZ == 3 && FM) return false;      // 4-wave 3x3 on the fragment-major image
+    if (NW == 4 && BM == 128 && KSZ == 3 && NC == 4 && PRO) return false;    // 128-pixel 3x3, 128 channels in
+    if (NW == 8 && BN == 32 && (BP || F32) && ((KSZ == 1 && NC == 16) || (KSZ == 3 && NC == 8))) return false;
+    if (F32 && NW == 4 && WK == 1 && BN == 64 && KSZ == 1 && NC == 1) return false;   // 128 -> 132 VGPRs: 4 -> 3 waves
+    return true;
+}
+
 // One 64-pixel x BN-channel output tile.  vb / nvb: the tile's virtual block
 // index and the virtual grid (= the tile count); a standalone launch passes
 // its blockIdx / gridDim, the persistent net chain (net_chain.hip) the tiles
@@ -77,6 +97,7 @@ __device__ __forceinline__ void deep_tile(const rnvp_conv_args& a, int shards, i
     constexpr int CPT = (NC * WK * KS + NT - 1) / NT;
     static_assert(!(BP && PRO), "BatchNorm-backward prologue: data gradients only");
     constexpr int NSTEP = KSZ * KSZ * NC;        // k-steps of one wave (static: fully unrolled)
+    constexpr bool STR = deep_stats_transposed<T, BN, KSZ, PRO, NW, WK, NC, FM, BM, BP>();
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, li = lane & 15;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wk = wid % WK, wm = wid / WK;
@@ -458,17 +479,25 @@ __device__ __forceinline__ void deep_tile(const rnvp_conv_args& a, int shards, i
     }
     DEEP_STAMP(4);
     if (want_sums) {
+        if constexpr (STR) {
+            // one transposing reduction of the thread's 8 NS partials: each sum's owning lane parks it
+            row_stats16(s1, s2, li, [&](int f, int r, int which, double u) {
+                const int cb = ((WK > 1 && !TALL) ? ((wid / TM) * FR + f) : f) * 16 + 4 * g;
+                sred[(grp * BN + cb + r) * 2 + which] = u;
+            });
+        } else {
 #pragma unroll
-        for (int f = 0; f < NS; ++f)
+            for (int f = 0; f < NS; ++f)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double u1 = row_sum16(s1[f][r]), u2 = row_sum16(s2[f][r]);
-                if (li == 0) {
-                    const int cb = ((WK > 1 && !TALL) ? ((wid / TM) * FR + f) : f) * 16 + 4 * g;
-                    sred[(grp * BN + cb + r) * 2] = u1;
-                    sred[(grp * BN + cb + r) * 2 + 1] = u2;
+                for (int r = 0; r < 4; ++r) {
+                    const double u1 = row_sum16(s1[f][r]), u2 = row_sum16(s2[f][r]);
+                    if (li == 0) {
+                        const int cb = ((WK > 1 && !TALL) ? ((wid / TM) * FR + f) : f) * 16 + 4 * g;
+                        sred[(grp * BN + cb + r) * 2] = u1;
+                        sred[(grp * BN + cb + r) * 2 + 1] = u2;
+                    }
                 }
-            }
+        }
         __syncthreads();
         double* sums = (epi_bn ? a.epi_sums : a.out_sums) + (long long)(vb % shards) * 2 * N;
         for (int col = tid; col < BN; col += NT) {

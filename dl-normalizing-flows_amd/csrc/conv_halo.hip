@@ -252,17 +252,10 @@ __global__ __launch_bounds__(256) void k_conv_halo(rnvp_conv_args a, int shards)
     }
     const bool want_sums = a.out_sums || (epi_bn && a.epi_sums);
     if (want_sums) {
-#pragma unroll
-        for (int f = 0; f < FR; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double u1 = row_sum16(s1[f][r]), u2 = row_sum16(s2[f][r]);
-                if (li == 0) {
-                    const int col = (fj0 + f) * 16 + 4 * g + r;
-                    sred[(fi * BN + col) * 2] = u1;
-                    sred[(fi * BN + col) * 2 + 1] = u2;
-                }
-            }
+        row_stats16(s1, s2, li, [&](int f, int r, int which, double u) {
+            const int col = (fj0 + f) * 16 + 4 * g + r;
+            sred[(fi * BN + col) * 2 + which] = u;
+        });
         __syncthreads();
         double* sums = (epi_bn ? a.epi_sums : a.out_sums) + (long long)(blockIdx.x % shards) * 2 * N;
         for (int col = tid; col < BN; col += 256) {

@@ -367,16 +367,9 @@ __global__ __launch_bounds__(256, (s1_min_blocks<NT, NKS, NOPS>())) void k_conv_
     // ---- batch statistics: DPP row sums, LDS across waves, sharded fp64 atomics ----
     const bool want_sums = a.out_sums || (epi_bn && a.epi_sums);
     if (want_sums) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double u1 = row_sum16((double)s1[j][r]), u2 = row_sum16((double)s2[j][r]);
-                if (li == 0) {
-                    red[wid][j * 16 + 4 * g + r][0] = u1;
-                    red[wid][j * 16 + 4 * g + r][1] = u2;
-                }
-            }
+        row_stats16(s1, s2, li, [&](int j, int r, int which, double u) {
+            red[wid][j * 16 + 4 * g + r][which] = u;
+        });
         __syncthreads();
         double* sums = shard_ptr(epi_bn ? a.epi_sums : a.out_sums, shards, N);
         for (int n = tid; n < N; n += 256) {
@@ -600,16 +593,9 @@ __global__ __launch_bounds__(256, 2) void k_s1_fanout(const rnvp_group_kargs gk)
     }
     if (sm >= 0) {
         const rnvp_conv_args& a = gk.conv[sm];
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double u1 = row_sum16((double)s1[j][r]), u2 = row_sum16((double)s2[j][r]);
-                if (li == 0) {
-                    red[(wid * NC + j * 16 + 4 * g + r) * 2] = u1;
-                    red[(wid * NC + j * 16 + 4 * g + r) * 2 + 1] = u2;
-                }
-            }
+        row_stats16(s1, s2, li, [&](int j, int r, int which, double u) {
+            red[(wid * NC + j * 16 + 4 * g + r) * 2 + which] = u;
+        });
         __syncthreads();
         double* sums = shard_ptr(a.out_sums, gk.shards[sm], a.n);
         for (int n = tid; n < a.n; n += 256) {

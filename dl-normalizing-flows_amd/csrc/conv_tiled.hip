@@ -207,17 +207,10 @@ __global__ __launch_bounds__(256) void k_conv(rnvp_conv_args a, int kt_per_split
         }
         if (want_sums) {
             double* sums = shard_ptr(a.epi_relu_bn_bwd ? a.epi_sums : a.out_sums, shards, N);
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double u1 = row_sum16(s1[j][r]), u2 = row_sum16(s2[j][r]);
-                    if (li == 0) {
-                        const int col = wn * WTN + j * 16 + 4 * g + r;
-                        red[(wm * BN + col) * 2] = u1;
-                        red[(wm * BN + col) * 2 + 1] = u2;
-                    }
-                }
+            row_stats16(s1, s2, li, [&](int j, int r, int which, double u) {
+                const int col = wn * WTN + j * 16 + 4 * g + r;
+                red[(wm * BN + col) * 2 + which] = u;
+            });
             __syncthreads();
             for (int col = tid; col < BN; col += 256) {
                 const int n = n0 + col;
