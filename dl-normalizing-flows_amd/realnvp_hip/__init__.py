@@ -10,7 +10,9 @@ Layout:
                  HIP-graph capture, RCCL data parallelism)
   optim.py       FusedAdam: torch.optim.Adam drop-in for the reference loop
   scorer.py      FlowScorer: per-image log-likelihoods (ragged batches, K-draw bound)
+  codec.py       FlowCodec: encode, decode, temperature sampling, interpolation
 """
 from ._lib import LIB_PATH, lib  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .scorer import FlowScorer  # noqa: F401
+from .codec import FlowCodec  # noqa: F401

@@ -111,6 +111,15 @@ class ScoreCtl(C.Structure):
                 ("n_valid", i32), ("n_draws", i32), ("draw", i32), ("overflow", i32)]
 
 
+RNVP_OUT_F32, RNVP_OUT_U8_ROUND, RNVP_OUT_U8_FLOOR = 0, 1, 2
+RNVP_MIX_LERP, RNVP_MIX_SLERP = 0, 1
+
+
+class LatentCtl(C.Structure):
+    _fields_ = [("dst", vp), ("cap", i64), ("first", i64), ("n_done", i64), ("temperature", f32),
+                ("n_valid", i32), ("overflow", i32), ("pad", i32)]
+
+
 WGRAD_GROUP_MAX = 24
 
 
@@ -242,6 +251,10 @@ _SIGS = {
     "rnvp_score_struct_size": (i32, []),
     "rnvp_score_in_fwd": (i32, [vp, vp, C.c_uint64, vp, f32, vp, vp, i32, i32, i32, i32, vp]),
     "rnvp_score_finish": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "rnvp_latent_struct_size": (i32, []),
+    "rnvp_latent_draw": (i32, [vp, C.c_uint64, vp, i32, i64, vp]),
+    "rnvp_latent_out": (i32, [vp, vp, f32, i32, i64, i32, vp]),
+    "rnvp_latent_mix": (i32, [vp, vp, vp, vp, i32, i32, i64, i32, vp, vp]),
     "rnvp_fill_f64": (i32, [vp, i64, f64, vp]),
     "rnvp_net_group_prepare": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "rnvp_net_group": (i32, [vp, i32, i32, i32, i32, i32, vp]),
@@ -262,6 +275,7 @@ class _Lib:
             raw = name in ("rnvp_version", "rnvp_struct_size", "rnvp_stat_shards", "rnvp_wgrad_slabs", "rnvp_wgrad_replicas",
                            "rnvp_link_nclass", "rnvp_conv2d_check", "rnvp_conv2d_family", "rnvp_wgrad_class", "rnvp_wgrad_multi_plan", "rnvp_wgrad_multi_struct_size",
                            "rnvp_grad_sumsq_parts", "rnvp_ema_struct_size", "rnvp_score_struct_size",
+                           "rnvp_latent_struct_size",
                            "rnvp_weight_norm_tiles", "rnvp_weight_norm_opt_blocks",
                            "rnvp_net_group_prepare") or res is not i32
             setattr(self, name[len("rnvp_"):], fn if raw else self._wrap(name, fn))
@@ -277,7 +291,8 @@ class _Lib:
             if self.dll.rnvp_wgrad_multi_struct_size(i) != C.sizeof(m):
                 raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"
                                    % (path, m.__name__, self.dll.rnvp_wgrad_multi_struct_size(i), C.sizeof(m)))
-        for m, size in ((EmaCtl, self.dll.rnvp_ema_struct_size()), (ScoreCtl, self.dll.rnvp_score_struct_size())):
+        for m, size in ((EmaCtl, self.dll.rnvp_ema_struct_size()), (ScoreCtl, self.dll.rnvp_score_struct_size()),
+                        (LatentCtl, self.dll.rnvp_latent_struct_size())):
             if size != C.sizeof(m):
                 raise RuntimeError("%s: struct %s is %d bytes in the library, %d in the binding (stale build?)"
                                    % (path, m.__name__, size, C.sizeof(m)))

@@ -771,6 +771,88 @@ int rnvp_score_in_fwd(const float* x, const float* noise /* may be NULL */, uint
 int rnvp_score_finish(const float* z, float* ldj, float* logdet, float* run, float* lp /* may be NULL */,
                       rnvp_score_ctl* ctl, int B, int n_per_sample, void* stream);
 
+/* ---- latents ---------------------------------------------------------------
+ * What a trained flow is used for besides scoring: draws from the prior that
+ * belong to the SAMPLE (not to its slot in the batch), the end of a decode
+ * into fp32 or bytes, interpolation between latents.  As in "scoring" one
+ * device-resident control block carries what changes between replays, so one
+ * captured graph serves every batch of every call: the host writes the block
+ * with stream-ordered copies / fills, rnvp_latent_out advances it, the
+ * library never reads it on the host.  (Encoding needs no entry point of its
+ * own: rnvp_score_in_fwd on a private rnvp_score_ctl with n_draws = 1,
+ * followed by the eval-mode forward.)
+ *
+ * rnvp_latent_draw: z[b][e] = ctl->temperature * g over [B][n], g a standard
+ * normal from ONE Philox4x32-10 call with counter ((first + b) * n + e, 0, 0)
+ * -- the 64-bit index in the first two words, low word first -- and key seed
+ * (low, high), as the uniform noise of rnvp_logit_fwd.  Of its four output
+ * words w0..w3:
+ *   u1 = ((w0 >> 8) + 1) * 2^-24   in (0, 1]
+ *   u2 = (w1 >> 8) * 2^-24         in [0, 1)
+ *   g  = sqrtf(-2 logf(u1)) * cosf(2 pi u2)       (|g| <= 5.77)
+ * in fp32 with the precise library functions.  An element is a function of
+ * (seed, its global index, temperature) alone: any batch size, any later call
+ * gives the same value.  Reads ctl, never writes it.
+ *
+ * rnvp_latent_out, a row kernel and then a one-workgroup advance: x is the
+ * inverse flow's output [B][n]; v = rnvp_logit_inv's value (the same fp32
+ * operations).  Row b < n_valid with 0 <= first + b < cap is stored at row
+ * first + b of dst (rows of n elements) as
+ *   RNVP_OUT_F32       v itself, unclamped (fp32; dst 4-byte aligned)
+ *   RNVP_OUT_U8_ROUND  (uint8) floor(clamp(255 v + 0.5, 0, 255)), the product
+ *                      and the sum rounded separately: torch's
+ *                      mul(255).add(0.5).clamp(0, 255).to(uint8), which is
+ *                      torchvision.utils.save_image's rule (train.py:259)
+ *   RNVP_OUT_U8_FLOOR  min(255, floor(256 clamp(v, 0, 1))): the exact inverse
+ *                      of the dequantisation (k + u) / 256, 0 <= u < 1
+ * Byte rows may start at any address (n need not be a multiple of 4): aligned
+ * 4-byte words with single bytes at both ends.  Rows >= n_valid, and rows
+ * past cap, store nothing.  The advance (its own launch behind the rows,
+ * which all read the block): overflow = 1 when first + n_valid > cap (no
+ * error status: the host reads the flag with the results), n_done += the rows
+ * stored, first += n_valid.
+ *
+ * rnvp_latent_mix: a, b [P][n] endpoint latents, t a DEVICE array of T floats,
+ * out [P][T][n]; out[p][j] = wa a[p] + wb b[p], the two products and the sum
+ * rounded separately in fp32 (so a weight pair (1, 0) returns a[p] itself),
+ * the weights formed in fp64 and rounded to fp32 once:
+ *   RNVP_MIX_LERP   wa = 1 - t, wb = t                       (ws may be NULL)
+ *   RNVP_MIX_SLERP  per pair a.b, |a|^2, |b|^2 in fp64 into ws (3 P doubles,
+ *                   caller-owned; the call zeroes what it needs zeroed);
+ *                   c = clamp(a.b / (|a| |b|), -1, 1); the lerp weights when
+ *                   1 - |c| < 1e-9 or a norm is zero; otherwise Om = acos(c),
+ *                   wa = sin((1 - t) Om) / sin Om, wb = sin(t Om) / sin Om
+ * The sums are per-workgroup partials: a pair of up to 16384 elements is one
+ * workgroup that stores its sums (no atomic, the same bits every time), a
+ * longer one at most 8 workgroups with one fp64 atomic each per sum.
+ *
+ * All three are stream-ordered, capture-safe, allocate nothing, and check
+ * their arguments before any HIP call: RNVP_E_INVALID for a NULL z / x / ctl
+ * (a / b / t / out; ws with RNVP_MIX_SLERP), a pointer that is not 4-byte
+ * (ctl, ws: 8-byte) aligned, B / P / T / n < 0, a B * n (P * T * n) beyond
+ * 2^63 - 1, P * T > 2^31 - 1, or an unknown mode.  A zero size is RNVP_OK
+ * with nothing launched.  0 <= n_valid <= B, first >= 0 and temperature >= 0
+ * are the writer's responsibility. */
+enum { RNVP_OUT_F32 = 0, RNVP_OUT_U8_ROUND = 1, RNVP_OUT_U8_FLOOR = 2 };
+enum { RNVP_MIX_LERP = 0, RNVP_MIX_SLERP = 1 };
+typedef struct rnvp_latent_ctl {
+    void* dst;              /* host: destination of the finished rows, cap rows of n elements (fp32 or uint8) */
+    long long cap;          /* host */
+    long long first;        /* global index of row 0 of the running batch; device-advanced */
+    long long n_done;       /* rows stored so far; device */
+    float temperature;      /* host: the prior's standard deviation (rnvp_latent_draw) */
+    int n_valid;            /* host: rows of the running batch that are real, 0..B */
+    int overflow;           /* device: set when first + n_valid > cap */
+    int pad;
+} rnvp_latent_ctl;
+/* sizeof(rnvp_latent_ctl), for a binding's mirror (the list of rnvp_struct_size is closed) */
+int rnvp_latent_struct_size(void);
+int rnvp_latent_draw(float* z, uint64_t seed, const rnvp_latent_ctl* ctl, int B, long long n, void* stream);
+int rnvp_latent_out(const float* x, rnvp_latent_ctl* ctl, float constraint, int B, long long n, int mode,
+                    void* stream);
+int rnvp_latent_mix(const float* a, const float* b, const float* t, float* out, int P, int T, long long n, int mode,
+                    double* ws /* RNVP_MIX_SLERP: 3 P doubles */, void* stream);
+
 /* ---- net steps ------------------------------------------------------------
  * One s/t-net step as a table entry (rnvp_net_group): a conv (rnvp_conv2d
  * semantics) or a BatchNorm-backward apply (rnvp_bn_bwd_apply semantics).
